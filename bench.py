@@ -38,7 +38,20 @@ cpu_baseline (rank 0, N=1): the plain-C oracle (oracle/, the CPU restatement,
 host core (P processes x 1 thread, each on its own cut of the grid, started
 together), run before the GPU is touched.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2] [--no-secondary]
+A plain run (python bench.py --gpus N --steps K --warmup W) sets the primary
+workload up, warms up, times the K steps and prints the JSON line with the
+headline figure (value, ms_per_step, the step's roofline from that time).
+--dump-outputs DIR also writes what the last timed step left in the prognostic
+fields (zeta, ubar, vbar, u, v, t of rank 0, as m.get() returns them: float64,
+whole when at most 2^20 elements, else a fixed seeded sample of 2^20) to
+DIR/<name>.npy; the analytic initial state makes two runs with the same
+arguments comparable array for array.  --full adds everything else: the CPU
+baselines, the secondary workload, the per-routine and per-kernel rooflines
+(eager steps of their own), the diag-norm blow-up check and, for N > 1, the
+halo-phase times and the exchange-order A/B.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                       [--workload c3|c2] [--no-secondary] [--no-cpu-baseline]
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N
 ranks itself (one process per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set
 before any GPU call) and relays rank 0's line; under torchrun it is one rank.
@@ -232,10 +245,32 @@ def launch_ranks(args, argv):
 
 
 # ---------------------------------------------------------------------------
+# --dump-outputs: the prognostic state after the last timed step
+# ---------------------------------------------------------------------------
+DUMP_FIELDS = ("zeta", "ubar", "vbar", "u", "v", "t")
+DUMP_MAX = 1 << 20   # elements per array: six float64 arrays of at most 8 MiB, 48 MiB in all
+DUMP_SEED = 1027
+
+
+def dump_outputs(m, outdir):
+    """Each field as Model.get() returns it (every time level, halo rows
+    included); past DUMP_MAX elements the same seeded, sorted sample of the
+    flattened array in every run."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for q, name in enumerate(DUMP_FIELDS):
+        a = m.get(name)
+        if a.size > DUMP_MAX:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, q]).integers(0, a.size, DUMP_MAX))
+            a = a.ravel()[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
+# ---------------------------------------------------------------------------
 # one workload on this rank
 # ---------------------------------------------------------------------------
 def run_workload(kind, romsgpu, comm, rank, world, local_rank, steps, warmup, timing_steps, barrier, allmax,
-                 step_only=False, gather=None):
+                 step_only=False, gather=None, full=True, dump_dir=None):
     npx, npe = proc_grid(world)
     c3 = kind == "c3"
     if c3:
@@ -261,12 +296,41 @@ def run_workload(kind, romsgpu, comm, rank, world, local_rank, steps, warmup, ti
     wall = time.perf_counter() - t0
     barrier()
     elapsed = allmax(max(wall, ev_ms / 1e3))
+    if dump_dir is not None and rank == 0:
+        dump_outputs(m, dump_dir)
     overlap = m.halo_overlap() if comm is not None else False
     s2d_window = m.s2d_window()
     if step_only:   # the whole-step time alone (the exchange-overlap A/B of a multi-rank run)
         m.close()
         return {"ms_per_step": 1e3 * elapsed / steps, "value": total_cells * steps / elapsed,
                 "steps": steps, "overlap": overlap}
+    transport = m.halo_transport() if comm is not None else "none (single rank)"
+    # exchanges per step (the fast loop's zeta/ubar/vbar swap every K fast steps)
+    exch, fast_k = m.halo_exchanges() if comm is not None else (0, 1)
+    ms_step = 1e3 * elapsed / steps
+    B = step_bytes(Lr, Mr, Nz, NT, NT_TS, nfast, lmd=c3)
+    step_gbs = B / (ms_step * 1e-3) / 1e9
+    res = {
+        "value": total_cells * steps / elapsed,
+        "ms_per_step": ms_step,
+        "model_seconds_per_wallclock_sec": steps * dt_step / elapsed,
+        "config": {"workload": ("C3: basin 1024x1024x100, NONLIN+SPLIT EOS, T+S, LMD KPP/BKPP/RIMIX/NONLOCAL, "
+                                "dt=300s, ndtfast=60 (nfast=%d)" % nfast) if c3 else
+                               "C2: Filament+S 512x512x50 per GPU, NT=2, dt=5s, ndtfast=60 (nfast=%d)" % nfast,
+                   "grid_per_gpu": [Lr, Mr, Nz], "proc_grid": [npx, npe], "NT": NT, "dt": dt_step, "nfast": nfast,
+                   "parallelism": "domain decomposition %dx%d" % (npx, npe), "halo_transport": transport,
+                   "halo_exchanges_per_step": exch, "fast_exchange_interval": fast_k,
+                   "exchange_order": ("deferred (3-D exchanges beside the next routine)" if overlap else
+                                      "in place" if comm is not None else "none (single rank)"),
+                   "s2d_window": s2d_window},
+        "scaling": "strong" if c3 else "weak",
+        "steps": steps, "warmup": warmup,
+        "roofline_step": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": step_gbs / HBM_PEAK_GBS, "bytes_per_step": B},
+    }
+    if not full:   # the headline figure alone: no eager timing steps, no diag reduction
+        m.close()
+        return res
     halo_time = None
     if comm is not None:
         # the halo path per rank: HIP events around every exchange's pack,
@@ -352,15 +416,12 @@ def run_workload(kind, romsgpu, comm, rank, world, local_rank, steps, warmup, ti
                           "launches_per_step": kn / timing_steps, "ms_per_step": kms * kn / timing_steps,
                           "passes": npass if npass is not None else "35 2-D"}
             c3k[kname].update(valu_issue(names, kms))
+    # read again after the eager timing steps, as the full line always has
     transport = m.halo_transport() if comm is not None else "none (single rank)"
-    # exchanges per step (the fast loop's zeta/ubar/vbar swap every K fast steps)
     exch, fast_k = m.halo_exchanges() if comm is not None else (0, 1)
     norms = m.diag()   # blow-up check as diag.F does (collective)
     if not all(x == x and abs(x) < 1e30 for x in norms):
         raise SystemExit("bench: non-finite diag norms %r" % norms)
-    ms_step = 1e3 * elapsed / steps
-    B = step_bytes(Lr, Mr, Nz, NT, NT_TS, nfast, lmd=c3)
-    step_gbs = B / (ms_step * 1e-3) / 1e9
     m.close()
     if not c3:
         # dominant kernel by time per step in the C2 kernel trace
@@ -378,33 +439,19 @@ def run_workload(kind, romsgpu, comm, rank, world, local_rank, steps, warmup, ti
         roofline = dict(c3k[dom_k])
         roofline["other_kernels"] = {k: v for k, v in c3k.items() if k != dom_k}
         roofline["trace_check"] = trace_top_kernel()
-    return {
-        "value": total_cells * steps / elapsed,
-        "ms_per_step": ms_step,
-        "model_seconds_per_wallclock_sec": steps * dt_step / elapsed,
-        "config": {"workload": ("C3: basin 1024x1024x100, NONLIN+SPLIT EOS, T+S, LMD KPP/BKPP/RIMIX/NONLOCAL, "
-                                "dt=300s, ndtfast=60 (nfast=%d)" % nfast) if c3 else
-                               "C2: Filament+S 512x512x50 per GPU, NT=2, dt=5s, ndtfast=60 (nfast=%d)" % nfast,
-                   "grid_per_gpu": [Lr, Mr, Nz], "proc_grid": [npx, npe], "NT": NT, "dt": dt_step, "nfast": nfast,
-                   "parallelism": "domain decomposition %dx%d" % (npx, npe), "halo_transport": transport,
-                   "halo_exchanges_per_step": exch, "fast_exchange_interval": fast_k,
-                   "exchange_order": ("deferred (3-D exchanges beside the next routine)" if overlap else
-                                      "in place" if comm is not None else "none (single rank)"),
-                   "halo_time_per_rank": halo_time,
-                   "s2d_window": s2d_window},
-        "scaling": "strong" if c3 else "weak",
-        "steps": steps, "warmup": warmup,
+    res["config"].update({"halo_time_per_rank": halo_time, "halo_transport": transport,
+                          "halo_exchanges_per_step": exch, "fast_exchange_interval": fast_k})
+    res.update({
         "roofline": roofline,
         "north_star_loop": north_star_loop,
         "roofline_routine": {"bound": "hbm", "achieved": D["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": D["frac"], "traffic": pmc_traffic(dom, c3),
                              "routine": dom + (" (one fast step: k_s2d_fb + edges + halo)" if dom == "step2d" else ""),
                              "bytes_per_launch": D["bytes_per_call"], "ms_per_launch": D["ms_per_call"]},
-        "roofline_step": {"bound": "hbm", "achieved": step_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": step_gbs / HBM_PEAK_GBS, "bytes_per_step": B},
         "routines": routines,
         "kernel_s2d_fb": kernel_fb,
-    }
+    })
+    return res
 
 
 def _pmc(c3=False):
@@ -501,11 +548,18 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--timing-steps", type=int, default=3, help="eager steps per routine for the event timings")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the secondary workload, per-routine and per-kernel rooflines, "
+                         "the diag-norm check and (N > 1) halo-phase times and the exchange-order A/B")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the prognostic fields after the last timed step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--workload", choices=("c2", "c3"), default="c3", help="the workload of the primary line")
     ap.add_argument("--no-secondary", "--no-c3", dest="no_secondary", action="store_true",
-                    help="skip the secondary workload's object (c2 under the default c3 line)")
+                    help="with --full: skip the secondary workload's object (c2 under the default c3 line)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the primary workload's timed steps and nothing else
+        args.no_cpu_baseline = args.no_secondary = True
     secondary = "c2" if args.workload == "c3" else "c3"
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -611,7 +665,8 @@ def main():
 
     try:
         prim = run_workload(args.workload, romsgpu, comm, rank, world, local_rank, args.steps, args.warmup,
-                            args.timing_steps, barrier, allmax, gather=gather)
+                            args.timing_steps, barrier, allmax, gather=gather, full=args.full,
+                            dump_dir=args.dump_outputs)
     except romsgpu.RomsGpuError as e:
         # the host channel carries no RCCL fallback: when the IPC transport
         # fails its set-up or self-test (a collective verdict, so every rank
@@ -622,9 +677,10 @@ def main():
         romsgpu.comm_destroy(comm)
         comm, bootstrap = rccl_comm(), "rccl (host-channel IPC self-test failed: %s)" % str(e)[:120]
         prim = run_workload(args.workload, romsgpu, comm, rank, world, local_rank, args.steps, args.warmup,
-                            args.timing_steps, barrier, allmax, gather=gather)
+                            args.timing_steps, barrier, allmax, gather=gather, full=args.full,
+                            dump_dir=args.dump_outputs)
     prim["config"]["comm_bootstrap"] = bootstrap
-    if comm is not None and world > 1 and os.environ.get("ROMS_GPU_XOVERLAP") is None:
+    if args.full and comm is not None and world > 1 and os.environ.get("ROMS_GPU_XOVERLAP") is None:
         # the deferred-exchange overlap (each producer's 3-D exchange beside
         # the next routine that reads none of its halo; the library's default
         # when every rank has its own GPU, in place when ranks share one,
@@ -660,7 +716,8 @@ def main():
         "model_seconds_per_wallclock_sec": prim["model_seconds_per_wallclock_sec"],
     }
     for k in ("roofline", "north_star_loop", "roofline_routine", "roofline_step", "routines", "kernel_s2d_fb"):
-        out[k] = prim[k]
+        if k in prim:   # a plain run has roofline_step alone
+            out[k] = prim[k]
     if args.workload in cpu:
         out["cpu_baseline"] = cpu[args.workload]
     if not args.no_secondary:

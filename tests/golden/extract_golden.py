@@ -1,5 +1,6 @@
 """Extract the per-step diag norms from the reference's golden logs into JSON
-fixtures.  Run in the build container (needs /root/reference); the JSON it
+fixtures, and the names of the subroutines src/main.F calls into
+main_F_calls.json.  Run in the build container (needs /root/reference); the JSON it
 writes is committed so tests never read /root/reference at run time.
 
 Column slicing follows tests/scripts/test_roms.py:100-103 of the reference:
@@ -8,6 +9,7 @@ MAX_ADV_CFL, MAX_VERT_CFL, printed ES23.16 by diag.F:552.
 """
 import json
 import os
+import re
 import sys
 
 REF = "/root/reference/tests"
@@ -53,6 +55,12 @@ def main():
         with open(os.path.join(out_dir, name + ".json"), "w") as f:
             json.dump({"source": "tests/" + rel, "ntimes": nt, "rows": rows}, f, indent=1)
         print(name, len(rows))
+    main_f = os.path.join(os.path.dirname(REF), "src", "main.F")
+    if os.path.exists(main_f):
+        calls = sorted({m.lower() for m in re.findall(r"^\s+call\s+(\w+)", open(main_f).read(), re.M | re.I)})
+        with open(os.path.join(out_dir, "main_F_calls.json"), "w") as f:
+            json.dump({"source": "src/main.F", "calls": calls}, f, indent=1)
+        print("main_F_calls", len(calls))
 
 
 if __name__ == "__main__":

@@ -42,12 +42,12 @@ REF = "/root/reference"
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference tree not present (container-only)")
-def test_dropins_compile_in_reference_tree_and_cover_main_calls():
+def test_dropins_compile_in_reference_tree_and_cover_main_calls(tmp_path):
     """SURVEY.md 8(b) callers 1: the drop-ins are compiled against the
     reference's own modules (case cppdefs.opt/param.opt over src/, cpp | mpc.py
     | amdflang), and the subroutines they define are exactly the hot-path
     routines roms_init / roms_step call (src/main.F:217-479)."""
-    out = "/tmp/roms_dropin_build_test"
+    out = str(tmp_path / "dropin_build")
     r = subprocess.run(["bash", os.path.join(FDIR, "refbuild", "build_dropins.sh"), os.path.join(REF, "tests", "Filament"),
                         out], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -57,6 +57,26 @@ def test_dropins_compile_in_reference_tree_and_cover_main_calls():
            "step3d_uv1", "step3d_uv2", "visc3d", "step2d", "step3d_t", "t3dmix"}
     called = {m.lower() for m in re.findall(r"^\s+call\s+(\w+)", main, re.M | re.I)} & hot
     assert called == hot, hot - called
+    assert built == {n + "_" for n in hot}, built ^ {n + "_" for n in hot}
+
+
+def test_dropins_built_in_tree_cover_recorded_main_calls():
+    """The same coverage without the reference tree: the subroutines main.F
+    calls are recorded in tests/golden/main_F_calls.json
+    (tests/golden/extract_golden.py), and the drop-ins compiled here against
+    the project's own stand-in modules (fortran/Makefile, seq_build/) define
+    exactly the hot-path routines among them."""
+    r = subprocess.run(["make", "-C", FDIR], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    hot = {"set_depth", "swr_frac", "set_huv", "set_huv1", "omega", "rho_eos", "lmd_vmix", "prsgrd", "pre_step3d",
+           "step3d_uv1", "step3d_uv2", "visc3d", "step2d", "step3d_t", "t3dmix"}
+    called = set(json.load(open(os.path.join(ROOT, "tests", "golden", "main_F_calls.json")))["calls"]) & hot
+    assert called == hot, hot - called
+    objs = [os.path.join(FDIR, "seq_build", os.path.splitext(f)[0] + ".o")
+            for f in sorted(os.listdir(os.path.join(FDIR, "dropin"))) if f.endswith(".F") and f != "roms_gpu_glue.F"]
+    nm = subprocess.run(["nm", "--defined-only"] + objs, capture_output=True, text=True, timeout=60)
+    assert nm.returncode == 0, nm.stderr
+    built = {ln.split()[2] for ln in nm.stdout.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"}
     assert built == {n + "_" for n in hot}, built ^ {n + "_" for n in hot}
 
 

@@ -34,26 +34,26 @@ suite)
   tail -1 $O/tests_$TAG.log
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1 || { echo SMOKEFAIL; tail -20 $O/smoke_$TAG.log; exit 1; }
   tail -1 $O/smoke_$TAG.log
-  timeout -k 10 500 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
+  timeout -k 10 500 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
   row $O/bench_$TAG.json bench ;;
 tests)
   timeout -k 10 1100 $PYT -v -rf -s "$@" > $O/tests_$TAG.log 2>&1; rc=$?
   tail -3 $O/tests_$TAG.log; exit $rc ;;
 bench)
-  timeout -k 10 600 python bench.py "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
+  timeout -k 10 600 python bench.py --full "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
   row $O/bench_$TAG.json "$TAG" ;;
 trace)
   W=${1:-c3}; M=k_step3d_t_seg; [ $W = c2 ] && M=k_step3d_t_v
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$TAG -o run -- python $R/bench.py --workload $W --steps 5 --warmup 1 --timing-steps 1 --no-cpu-baseline --no-secondary > $O/kt_$TAG.json 2> $O/kt_$TAG.err || { tail -5 $O/kt_$TAG.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$TAG -o run -- python $R/bench.py --full --workload $W --steps 5 --warmup 1 --timing-steps 1 --no-cpu-baseline --no-secondary > $O/kt_$TAG.json 2> $O/kt_$TAG.err || { tail -5 $O/kt_$TAG.err; exit 1; }
   python3 $R/tools/prof_summary.py $(find $O/kt_$TAG -name "*kernel_trace.csv") --steps 4 --marker $M > $O/kt_$TAG.txt 2>&1
   head -30 $O/kt_$TAG.txt ;;
 pmc)
   cd /tmp && export TMPDIR=/tmp
   export ROMS_GPU_NO_GRAPH=1
   for W in c2 c3; do
-    if [ $W = c2 ]; then B="python $R/bench.py --no-cpu-baseline --no-secondary --workload c2 --timing-steps 1 --steps 4 --warmup 1"; M=k_step3d_t_v
-    else B="python $R/bench.py --no-cpu-baseline --no-secondary --workload c3 --timing-steps 1 --steps 2 --warmup 1"; M=k_step3d_t_segb; fi
+    if [ $W = c2 ]; then B="python $R/bench.py --full --no-cpu-baseline --no-secondary --workload c2 --timing-steps 1 --steps 4 --warmup 1"; M=k_step3d_t_v
+    else B="python $R/bench.py --full --no-cpu-baseline --no-secondary --workload c3 --timing-steps 1 --steps 2 --warmup 1"; M=k_step3d_t_segb; fi
     timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pt_f_$W -o run -- $B > $O/pt_f_$W.log 2>&1 || exit 1
     timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pt_w_$W -o run -- $B > $O/pt_w_$W.log 2>&1 || exit 1
     python3 $R/tools/pmc_traffic.py $(find $O/pt_f_$W -name '*counter_collection.csv') $(find $O/pt_w_$W -name '*counter_collection.csv') \
@@ -82,7 +82,7 @@ ab)
       env:*) E=$(echo "${v#env:}" | tr ',' ' ') ;;
     esac
     n=$(echo "$v" | tr -c 'A-Za-z0-9_' '_')
-    env $E timeout -k 10 400 python bench.py $(wargs $W) --no-cpu-baseline > $O/ab_${TAG}_$n.json 2> $O/ab_${TAG}_$n.err || { echo "$v BENCHFAIL"; tail -20 $O/ab_${TAG}_$n.err; exit 1; }
+    env $E timeout -k 10 400 python bench.py --full $(wargs $W) --no-cpu-baseline > $O/ab_${TAG}_$n.json 2> $O/ab_${TAG}_$n.err || { echo "$v BENCHFAIL"; tail -20 $O/ab_${TAG}_$n.err; exit 1; }
     row $O/ab_${TAG}_$n.json "$v"
   done ;;
 stall)
@@ -91,7 +91,7 @@ valu)
   # VALU instruction mix per kernel at C3 (one --pmc pass of 8 SQ counters)
   cd /tmp && export TMPDIR=/tmp
   export ROMS_GPU_NO_GRAPH=1
-  B="python $R/bench.py --no-cpu-baseline --no-secondary --workload c3 --timing-steps 1 --steps 2 --warmup 1"
+  B="python $R/bench.py --full --no-cpu-baseline --no-secondary --workload c3 --timing-steps 1 --steps 2 --warmup 1"
   timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 --output-format csv -d $O/pv_$TAG -o run -- $B > $O/pv_$TAG.log 2>&1 || exit 1
   python3 $R/tools/pmc_valu.py $(find $O/pv_$TAG -name '*counter_collection.csv') --out $O/pmc_valu_c3.json || exit 1 ;;
 final)
@@ -100,7 +100,7 @@ final)
   # and VALU tables + the 2-rank one-GPU rehearsal
   PART=${1:-1}
   if [ "$PART" = 1 ]; then
-    timeout -k 10 500 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
+    timeout -k 10 500 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err || { echo BENCHFAIL; tail -20 $O/bench_$TAG.err; exit 1; }
     row $O/bench_$TAG.json bench
     bash $R/tools/gpu.sh trace ${TAG}_c3 c3 || exit 1
     bash $R/tools/gpu.sh trace ${TAG}_c2 c2 || exit 1
@@ -108,7 +108,7 @@ final)
     bash $R/tools/gpu.sh pmc x || exit 1
     bash $R/tools/gpu.sh valu $TAG || exit 1
     cd $R
-    timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > $O/bench_${TAG}_n2.json 2> $O/bench_${TAG}_n2.err || { tail -10 $O/bench_${TAG}_n2.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --gpus 2 --steps 5 --warmup 1 --no-cpu-baseline --no-secondary > $O/bench_${TAG}_n2.json 2> $O/bench_${TAG}_n2.err || { tail -10 $O/bench_${TAG}_n2.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/bench_${TAG}_n2.json')); print('n2', d['ms_per_step'], d['config'].get('exchange_overlap'))"
   fi ;;
 *) echo "usage: bash tools/gpu.sh suite|tests|bench|trace|pmc|ab|stall|final TAG ..."; exit 2 ;;
