@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 16
+#define ROMS_GPU_ABI_VERSION 17
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -298,6 +298,16 @@ int roms_gpu_halo_overlap(void);
  * 0 if through their pointers (ROMS_GPU_S2D_WIN=0, or a subdomain whose
  * 2-D fields span more).  Same results either way.                         */
 int roms_gpu_s2d_window(void);
+/* Which vertical column solvers this model runs, chosen at init from N:
+ * bit 0 (ROMS_COLPATH_SEG): the segment-partitioned solvers (default where
+ * the sequential solvers' LDS columns no longer fit and every segment gets
+ * its minimum of rows; ROMS_GPU_COLSEG=0/1 forces either where N allows);
+ * bit 1 (ROMS_COLPATH_GLOBAL): the sequential solvers' column scratch lives
+ * in global memory instead of LDS (default for N >= 64;
+ * ROMS_GPU_COL_GLOBAL=0/1).  Negative before init.                        */
+#define ROMS_COLPATH_SEG 1
+#define ROMS_COLPATH_GLOBAL 2
+int roms_gpu_column_path(void);
 /* Self-test of the allocation path: `chunks` arrays of n doubles filled
  * with ones and freed, then allocated again through the library's
  * zero-filling allocator; on the library's stream each is read at once

@@ -1319,6 +1319,11 @@ int roms_gpu_s2d_window(void) {
   return g.d.w2.base ? 1 : 0;
 }
 
+int roms_gpu_column_path(void) {
+  REQUIRE_INIT_NOJOIN();
+  return (g.d.p.colseg ? ROMS_COLPATH_SEG : 0) | (g.d.f.colscr ? ROMS_COLPATH_GLOBAL : 0);
+}
+
 int roms_gpu_halo_exchanges(long* per_step, int* fast_interval) {
   REQUIRE_INIT_NOJOIN();
   if (per_step) *per_step = g.step_exch;

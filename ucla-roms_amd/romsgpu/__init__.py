@@ -544,6 +544,13 @@ class Model:
         buffer window (roms_gpu_s2d_window; ROMS_GPU_S2D_WIN=0: pointers)."""
         return bool(self.L.roms_gpu_s2d_window())
 
+    def column_path(self):
+        """(segment solvers on, column scratch in global memory) as chosen at
+        init from N, ROMS_GPU_COLSEG and ROMS_GPU_COL_GLOBAL (roms_gpu_column_path)."""
+        r = self.L.roms_gpu_column_path()
+        self._chk(min(r, 0), "column_path")
+        return bool(r & 1), bool(r & 2)
+
     def halo_exchanges(self):
         """(exchanges in the last enqueued step, fast-loop exchange interval)
         -- roms_gpu_halo_exchanges."""
