@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 17
+#define ROMS_GPU_ABI_VERSION 18
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -308,6 +308,22 @@ int roms_gpu_s2d_window(void);
 #define ROMS_COLPATH_SEG 1
 #define ROMS_COLPATH_GLOBAL 2
 int roms_gpu_column_path(void);
+/* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
+ * edges and the ROMS_GPU_* switches by the same host functions the launchers
+ * call:
+ *   out[0]  the fast step's closed-edge mode: 0 no closed or open edge on
+ *           this rank, 1 separate edge launches (k_s2d_edges), 2 the closed
+ *           walls folded into the fused fast step;
+ *   out[1]  1 if the prsgrd calls of a whole step take the j-marching strips
+ *           (k_prsgrd_strip) for some rows, 0 if tiles everywhere;
+ *   out[2]  strips per row (each owns 60 columns), 0 without strips;
+ *   out[3], out[4]  first and last strip row jA, jB (0, -1 without strips;
+ *           the other rows of 1..Mm run in tiles);
+ *   out[5]  1 if omega takes the segment form (k_omega_seg: 32 columns or
+ *           more and N within the segment solvers' depth), 0: two-pass k_omega;
+ *   out[6], out[7]  reserved, 0.
+ * Negative before init.                                                      */
+int roms_gpu_horizontal_path(int out[8]);
 /* Self-test of the allocation path: `chunks` arrays of n doubles filled
  * with ones and freed, then allocated again through the library's
  * zero-filling allocator; on the library's stream each is read at once

@@ -80,6 +80,25 @@ def test_uninitialised_calls_fail_loudly():
         m.omega()
 
 
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libromsgpu.so not built")
+def test_path_reports_fail_before_init():
+    """roms_gpu_column_path / roms_gpu_horizontal_path report a live model's
+    dispatch; without one they return an error and leave the output alone."""
+    import romsgpu
+    m = romsgpu.Model()
+    with pytest.raises(romsgpu.RomsGpuError):
+        m.column_path()
+    with pytest.raises(romsgpu.RomsGpuError):
+        m.horizontal_path()
+    out = (ctypes.c_int * 8)(*[7] * 8)
+    assert m.L.roms_gpu_horizontal_path(out) < 0 and list(out) == [7] * 8
+
+
+def test_fortran_module_declares_horizontal_path():
+    f = open(os.path.join(ROOT, "fortran", "roms_gpu_mod.F90")).read()
+    assert re.search(r"function roms_gpu_horizontal_path\(out\) bind\(c\)", f)
+
+
 def test_fortran_module_abi_version_matches_header():
     """fortran/roms_gpu_mod.F90's ROMS_GPU_ABI must follow ROMS_GPU_ABI_VERSION."""
     import re

@@ -108,24 +108,30 @@ def depth_model(cfg, forced=False, col_global=None):
 
 
 def routine_list(cfg):
-    """(id, routine, mode, outputs): test_gpu_parity's ROUTINE_CASES and
-    lmd_vmix at both time indices (test_gpu_lmd)."""
+    """(id, routine, mode, outputs): test_gpu_parity's ROUTINE_CASES and, with
+    KPP on, lmd_vmix at both time indices (test_gpu_lmd)."""
     out = []
     for name, mode, outs in ROUTINE_CASES:
         if name == "rho_eos" and cfg.nonlin_eos:
             outs = ["rho1", "qp1", "rhoA", "rhoS"]
         out.append((name, name, mode, outs))
-    out.append(("lmd_vmix_nstp", "lmd_vmix", None, LMD_OUT))
-    out.append(("lmd_vmix_nrhs", "lmd_vmix", "corr", LMD_OUT))
+    if cfg.lmd:
+        out.append(("lmd_vmix_nstp", "lmd_vmix", None, LMD_OUT))
+        out.append(("lmd_vmix_nrhs", "lmd_vmix", "corr", LMD_OUT))
     return out
 
 
-@functools.lru_cache(maxsize=1)
-def routine_case(N):
-    """The oracle after 3 steps with perturbed mixing and implicit fluxes,
-    a copy of its whole state, and the per-routine reference outputs
-    (filled on first use, shared by the default and the forced model)."""
-    cfg = depth_cfg(N)
+_ROUTINE_CASE = {}   # one entry: the configuration last asked for
+
+
+def routine_case(cfg):
+    """The oracle of configuration cfg after 3 steps with perturbed mixing and
+    implicit fluxes, a copy of its whole state, and the per-routine reference
+    outputs (filled on first use, shared by every model of the same
+    configuration that follows: the default and the forced one)."""
+    key = bytes(cfg)
+    if key in _ROUTINE_CASE:
+        return _ROUTINE_CASE[key]
     o = oracle.Oracle(cfg)
     o.init()
     o.step(3)
@@ -136,15 +142,17 @@ def routine_case(N):
     we, wi = o.field("We"), o.field("Wi")
     wi[...] = wi + 0.01 * float(np.abs(we).max()) * rng.standard_normal(wi.shape)
     snap = {n: o.field(n).copy() for n in romsgpu.FIELDS}
-    return cfg, o, snap, o.tindex(), {}
+    _ROUTINE_CASE.clear()
+    _ROUTINE_CASE[key] = cfg, o, snap, o.tindex(), {}
+    return _ROUTINE_CASE[key]
 
 
-def routine_errors(N, m, only=None):
-    """Every routine on the same state, oracle and GPU: {(id, field): error}
-    relative to the field's interior maximum (Wi: to We's, as in
-    test_gpu_colseg.test_omega_blocks -- where the Courant split leaves Wi
-    zero it is cancellation noise)."""
-    cfg, o, snap, tix, refs = routine_case(N)
+def routine_errors(cfg, m, only=None):
+    """Every routine on the same state of configuration cfg, oracle and GPU:
+    {(id, field): error} relative to the field's interior maximum (Wi: to
+    We's, as in test_gpu_colseg.test_omega_blocks -- where the Courant split
+    leaves Wi zero it is cancellation noise)."""
+    cfg, o, snap, tix, refs = routine_case(cfg)
     iic, kstp, knew, nstp = tix[:4]
     errs = {}
     for rid, routine, mode, outs in routine_list(cfg):
@@ -181,9 +189,10 @@ def routine_errors(N, m, only=None):
 def test_depth_routine_parity(N, forced):
     """Each routine at depth N within RTOL_ROUTINE of the oracle (DEPTHS[N]
     names the paths); every failing (routine, field, error) is reported at once."""
-    m = depth_model(depth_cfg(N), forced)
+    cfg = depth_cfg(N)
+    m = depth_model(cfg, forced)
     try:
-        errs = routine_errors(N, m)
+        errs = routine_errors(cfg, m)
     finally:
         m.close()
     for (rid, f), e in errs.items():

@@ -1,10 +1,10 @@
-"""The j-marching strip kernels (the defaults in whole steps) against the
-tiles they replace, whole runs bitwise equal:
-  * prsgrd's ru/rv with the momentum r.h.s. (k_prsgrd_strip.hip) against the
-    k_prsgrd_uv tiles (ROMS_GPU_PRS_STRIP=0);
+"""The j-marching strip kernels against the tiles they replace, whole runs
+bitwise equal:
+  * prsgrd's ru/rv with the momentum r.h.s. (k_prsgrd_strip.hip, the default
+    in whole steps) against the k_prsgrd_uv tiles (ROMS_GPU_PRS_STRIP=0);
   * the horizontal tracer advection of pre_step3d and step3d_t
-    (k_tracer_strip.hip) against the k_pre_tracer_h1 / k_step3d_t_h1 tiles
-    (ROMS_GPU_T_STRIP=0).
+    (k_tracer_strip.hip, opt-in: ROMS_GPU_T_STRIP=1, roms_shim.cpp P.t_strip)
+    against the k_pre_tracer_h1 / k_step3d_t_h1 tiles, the default.
 
 The strips evaluate each elementary difference, harmonic mean and advective
 flux once per face and take the i-neighbours' values through DPP lane shifts;

@@ -14,8 +14,9 @@
 namespace roms {
 
 // k_prsgrd_strip.hip: rows jA..jB of the fused form in j-marching strips
-bool launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin, int imax, int jmin, int jmax,
-                         const UVBounds& ub, int& jA, int& jB);
+bool prsgrd_strip_rows(const Dev& d, int jmin, int jmax, const UVBounds& ub, int& jA, int& jB, int& nstrip);
+void launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin, int imax, const UVBounds& ub, int jA,
+                         int jB);
 
 __device__ __forceinline__ double harm(double a, double b) {
   const double c = 2.0 * a * b;
@@ -661,11 +662,8 @@ void launch_prsgrd_P(const Dev& d, hipStream_t s) {
   Range R1{0, b.Lm, 0, b.Mm};
   hipLaunchKernelGGL(k_prsgrd_P, grid_of(R1), dim3(kBX, kBY), 0, s, d, R1, d.p.nonlin_eos, d.p.tides);
 }
-void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up, bool p_ready) {
-  const Bounds& b = d.b;
-  if (d.p.iso && t.nrhs == 3) launch_iso_slopes(d, s);   // ADV_ISONEUTRAL, CORR_STAGE (prsgrd.F:307-338)
-  const int split = d.p.nonlin_eos;
-  int imin, imax, jmin, jmax;
+// FC / rx extrapolation ranges (prsgrd.F:229-240, 345-356)
+static void prsgrd_extrap_bounds(const Bounds& b, int& imin, int& imax, int& jmin, int& jmax) {
   if (!b.ew_periodic) {
     imin = b.west_edge ? b.istrU : b.istrU - 1;
     imax = b.east_edge ? b.iend : b.iend + 1;
@@ -674,6 +672,24 @@ void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up, bool p
     jmin = b.south_edge ? b.jstrV : b.jstrV - 1;
     jmax = b.north_edge ? b.jend : b.jend + 1;
   } else { jmin = b.jstr - 1; jmax = b.jend + 1; }
+}
+// whether a prsgrd call takes the j-marching strips (with_uv: it also forms
+// the momentum r.h.s., as every prsgrd of a whole step does when
+// prsgrd_can_fuse_uv), their rows jA..jB and the strips per row
+// (launch_prsgrd, roms_gpu_horizontal_path)
+bool prsgrd_takes_strips(const Dev& d, bool with_uv, int& jA, int& jB, int& nstrip) {
+  int imin, imax, jmin, jmax;
+  prsgrd_extrap_bounds(d.b, imin, imax, jmin, jmax);
+  jA = 0; jB = -1; nstrip = 0;
+  return with_uv && d.p.prs_split && d.p.prs_strip && d.p.uv_cor && d.p.uv_adv && !d.p.curvgrid &&
+         prsgrd_strip_rows(d, jmin, jmax, uv_bounds(d.b), jA, jB, nstrip);
+}
+void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up, bool p_ready) {
+  const Bounds& b = d.b;
+  if (d.p.iso && t.nrhs == 3) launch_iso_slopes(d, s);   // ADV_ISONEUTRAL, CORR_STAGE (prsgrd.F:307-338)
+  const int split = d.p.nonlin_eos;
+  int imin, imax, jmin, jmax;
+  prsgrd_extrap_bounds(b, imin, imax, jmin, jmax);
   Range R2{b.istr, b.iend, b.jstr, b.jend};
   if (!d.p.prs_split) {
     hipLaunchKernelGGL(k_prsgrd_fused, grid_of(R2), dim3(kFT), 0, s, d, R2, split, imin, imax, jmin, jmax, d.p.tides);
@@ -709,9 +725,9 @@ void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up, bool p
   // with the momentum r.h.s. (whole steps): rows jA..jB in j-marching strips
   // (k_prsgrd_strip.hip), the bands of rows a closed-edge j-extrapolation
   // reaches in k_prsgrd_uv tiles; ROMS_GPU_PRS_STRIP=0: tiles everywhere
-  int jA = 0, jB = -1;
-  if (uv_up >= 0 && d.p.prs_strip && d.p.uv_cor && d.p.uv_adv && !d.p.curvgrid &&
-      launch_prsgrd_strip(d, s, t.nrhs, uv_up, imin, imax, jmin, jmax, uv_bounds(b), jA, jB)) {
+  int jA = 0, jB = -1, nstrip = 0;
+  if (prsgrd_takes_strips(d, uv_up >= 0, jA, jB, nstrip)) {
+    launch_prsgrd_strip(d, s, t.nrhs, uv_up, imin, imax, uv_bounds(b), jA, jB);
     if (jA > R2.j0) tiles(Range{R2.i0, R2.i1, R2.j0, jA - 1});
     if (jB < R2.j1) tiles(Range{R2.i0, R2.i1, jB + 1, R2.j1});
   } else {

@@ -284,10 +284,10 @@ __global__ void __launch_bounds__(64, ROMS_PRS_STRIP_WAVES) k_prsgrd_strip(Dev d
   }
 }
 
-// ru, rv of rows jA..jB (every column istr..iend) in strips; false if the
-// configuration is not one this kernel covers (the caller runs k_prsgrd_uv)
-bool launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin, int imax, int jmin, int jmax,
-                         const UVBounds& ub, int& jA, int& jB) {
+// The rows jA..jB the strips cover and the strips per row (launch_prsgrd,
+// roms_gpu_horizontal_path); false if the configuration is not one the kernel
+// covers (k_prsgrd_uv tiles then run everywhere)
+bool prsgrd_strip_rows(const Dev& d, int jmin, int jmax, const UVBounds& ub, int& jA, int& jB, int& nstrip) {
   const Bounds& b = d.b;
   // rows whose stencils no j-extrapolation reaches (FC: jmin..jmax; vee,
   // Hvee: v_jmin..v_jmax; uee: e_jmin..e_jmax) and whose ru, rv both exist
@@ -297,7 +297,16 @@ bool launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin
   jB = std::min(std::min(jmax, ub.v_jmax), ub.e_jmax) - 1;
   jB = std::min(jB, b.jend);
   jB = std::min(jB, b.Mm);   // rows ..jB+2 are read
+  nstrip = (b.iend - b.istr + kStripOwn) / kStripOwn;
   if (jB < jA) return false;
+  return b.istr - 2 >= -1;   // lane 0 of strip 0 reads column istr - 2
+}
+
+// ru, rv of rows jA..jB (every column istr..iend) in strips: the rows
+// prsgrd_strip_rows gave
+void launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin, int imax, const UVBounds& ub, int jA,
+                         int jB) {
+  const Bounds& b = d.b;
   StripGeom G;
   G.c00 = b.istr - 2;
   G.ilast = b.iend;
@@ -307,7 +316,6 @@ bool launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin
   G.ximin = ub.x_imin; G.ximax = ub.x_imax;
   G.xlo = std::max(std::max(imin, ub.u_imin), ub.x_imin);
   G.xhi = std::min(std::min(imax, ub.u_imax), ub.x_imax);
-  if (G.c00 < -1) return false;   // lane 0 reads column c0
   constexpr int J = ROMS_PRS_STRIP_J;
   const dim3 grid((unsigned)((b.iend - b.istr + kStripOwn) / kStripOwn), (unsigned)((jB - jA + J) / J), (unsigned)b.N);
   const int split = d.p.nonlin_eos;
@@ -315,7 +323,6 @@ bool launch_prsgrd_strip(const Dev& d, hipStream_t s, int nrhs, int up, int imin
   else if (split) hipLaunchKernelGGL((k_prsgrd_strip<true, false, J>), grid, dim3(64), 0, s, d, G, nrhs);
   else if (up) hipLaunchKernelGGL((k_prsgrd_strip<false, true, J>), grid, dim3(64), 0, s, d, G, nrhs);
   else hipLaunchKernelGGL((k_prsgrd_strip<false, false, J>), grid, dim3(64), 0, s, d, G, nrhs);
-  return true;
 }
 
 }  // namespace roms

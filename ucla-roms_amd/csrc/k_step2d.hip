@@ -1024,12 +1024,11 @@ void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1,
   launch_exchange_list(d, s, L);
 }
 
-// one fast step's kernels over the bounds of d (launch_step2d): the fused
-// step (or the split form), then the open / closed edges
-void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& t) {
+// the fast step's closed-edge mode (launch_fast_step, roms_gpu_horizontal_path):
+// 0 no edge of this rank, 1 separate k_s2d_edges launches, 2 folded into k_s2d_fb
+int s2d_edge_mode(const Dev& d) {
   const Bounds& b = d.b;
   const bool closed = b.west_edge || b.east_edge || b.south_edge || b.north_edge;
-  Range RB{b.istrR, b.iendR, b.jstrR, b.jendR};
   // closed walls folded into k_s2d_fb when no edge is open and every edge
   // row / column shares its tile with the interior row / column beside it
   // (tiles start at tile_i0(istrR) / jstrR; ROMS_GPU_S2D_EDGES=1 keeps k_s2d_edges)
@@ -1037,7 +1036,17 @@ void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& 
                     (!b.east_edge || (b.iendR - tile_i0(b.istrR)) % kBX != 0) &&
                     (!b.west_edge || (b.istrR - tile_i0(b.istrR)) % kBX != kBX - 1) &&
                     (!b.north_edge || (b.jendR - b.jstrR) % kBY != 0);
-  const int cmode = !closed ? 0 : (fold ? 2 : 1);
+  return !closed ? 0 : (fold ? 2 : 1);
+}
+
+// one fast step's kernels over the bounds of d (launch_step2d): the fused
+// step (or the split form), then the open / closed edges
+void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& t) {
+  const Bounds& b = d.b;
+  const bool closed = b.west_edge || b.east_edge || b.south_edge || b.north_edge;
+  Range RB{b.istrR, b.iendR, b.jstrR, b.jendR};
+  const int cmode = s2d_edge_mode(d);
+  const bool fold = cmode == 2;
   Halo* H = const_cast<Halo*>(d.halo);   // multi-rank exchange state (host bookkeeping)
   // single rank (no halo exchange object) with the fused kernel: periodic
   // halos of the fast-time fields are read through their images

@@ -646,6 +646,12 @@ static void omega_seg(const Dev& d, hipStream_t s, const Range& r, double dtau, 
 // hcff > 0 (the predictor's call): also form pre_step3d's Hz_bak / Hz_fwd of
 // the interior cells into c3 / c2 with 0.5*dtau = hcff (k_omega_seg<true>);
 // returns whether it did (one segment launch over the whole interior)
+// whether omega over a range `width` columns wide takes the segment form
+// k_omega_seg (launch_omega, roms_gpu_horizontal_path); narrower ranges and
+// deeper grids take the two-pass k_omega
+bool omega_takes_seg(const Dev& d, int width) {
+  return d.p.omega_seg && d.b.N <= kSegRows * kSegMaxS && width >= 32;
+}
 bool launch_omega(const Dev& d, hipStream_t s, const Tlev& t, double hcff) {
   const Bounds& b = d.b;
   double dtau;
@@ -653,15 +659,14 @@ bool launch_omega(const Dev& d, hipStream_t s, const Tlev& t, double hcff) {
   else if (t.iic == t.forw_start) dtau = 0.5 * d.p.dt;
   else dtau = 0.6 * d.p.dt;
   Range R{b.istr, b.iend, b.jstr, b.jend};
-  const bool seg_ok = d.p.omega_seg && b.N <= kSegRows * kSegMaxS;
-  const bool hb = hcff > 0.0 && seg_ok && R.i1 - R.i0 + 1 >= 32 && !rim_overlap_on(d, R);
+  const bool hb = hcff > 0.0 && omega_takes_seg(d, R.i1 - R.i0 + 1) && !rim_overlap_on(d, R);
   launch_rim_first(
       d, s, R, ExchList{{d.f.We, d.f.Wi}, {b.N + 1, b.N + 1}, 2},
       [&](const Range& r) {
         // the segment form for full-width ranges (rim strips keep k_omega)
         if (hb)
           omega_seg<true>(d, s, r, dtau, hcff);
-        else if (seg_ok && r.i1 - r.i0 + 1 >= 32)
+        else if (omega_takes_seg(d, r.i1 - r.i0 + 1))
           omega_seg<false>(d, s, r, dtau, 0.0);
         else
           hipLaunchKernelGGL(k_omega, grid_of(r), dim3(kBX, kBY), 0, s, d, r, dtau);

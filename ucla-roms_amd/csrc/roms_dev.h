@@ -440,6 +440,15 @@ void launch_set_huv1(const Dev& d, hipStream_t s, const Tlev& t);
 // interior cells with 0.5*dtau = hcff; returns whether it did (k_vertical.hip)
 bool launch_omega(const Dev& d, hipStream_t s, const Tlev& t, double hcff = 0.0);
 void setup_omega_seg();   // k_omega_seg<true>'s dynamic LDS limit
+// The horizontal path decisions, shared by the launchers and
+// roms_gpu_horizontal_path: omega's segment form over a range `width` columns
+// wide (k_vertical.hip); the fast step's closed-edge mode, 0 none / 1 separate
+// k_s2d_edges launches / 2 folded into k_s2d_fb (k_step2d.hip); whether a
+// prsgrd call (with_uv: with the momentum r.h.s.) takes the j-marching
+// strips, their rows jA..jB and the strips per row (k_prsgrd.hip)
+bool omega_takes_seg(const Dev& d, int width);
+int s2d_edge_mode(const Dev& d);
+bool prsgrd_takes_strips(const Dev& d, bool with_uv, int& jA, int& jB, int& nstrip);
 double pre_step3d_dtau(const Dev& d, const Tlev& t);   // pre_step3d's dtau (k_pre_step3d.hip)
 void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx);
 // uv_up >= 0: also add the horizontal momentum r.h.s. (UPSTREAM_UV if 1) of

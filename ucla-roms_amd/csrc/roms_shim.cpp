@@ -1324,6 +1324,23 @@ int roms_gpu_column_path(void) {
   return (g.d.p.colseg ? ROMS_COLPATH_SEG : 0) | (g.d.f.colscr ? ROMS_COLPATH_GLOBAL : 0);
 }
 
+int roms_gpu_horizontal_path(int out[8]) {
+  REQUIRE_INIT_NOJOIN();
+  if (!out) { g.err = "roms_gpu_horizontal_path: null argument"; return -1; }
+  const Dev& d = g.d;
+  int jA = 0, jB = -1, nstrip = 0;
+  // every prsgrd of a whole step carries the momentum r.h.s. when it can (enqueue_step)
+  const bool strips = prsgrd_takes_strips(d, prsgrd_can_fuse_uv(d), jA, jB, nstrip);
+  out[0] = s2d_edge_mode(d);
+  out[1] = strips ? 1 : 0;
+  out[2] = strips ? nstrip : 0;
+  out[3] = strips ? jA : 0;
+  out[4] = strips ? jB : -1;
+  out[5] = omega_takes_seg(d, d.b.iend - d.b.istr + 1) ? 1 : 0;
+  out[6] = out[7] = 0;
+  return 0;
+}
+
 int roms_gpu_halo_exchanges(long* per_step, int* fast_interval) {
   REQUIRE_INIT_NOJOIN();
   if (per_step) *per_step = g.step_exch;

@@ -131,6 +131,7 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_comm_create_host.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, HOST_ALLGATHER_FN,
                                             ctypes.c_void_p, P(ctypes.c_void_p)]
     L.roms_gpu_comm_destroy.argtypes = [ctypes.c_void_p]
+    L.roms_gpu_horizontal_path.argtypes = [P(ctypes.c_int)]
     L.roms_gpu_halo_plan.argtypes = [ctypes.c_int] * 8 + [P(ctypes.c_int), P(ctypes.c_long), P(ctypes.c_int)]
     L.roms_gpu_halo_map.argtypes = [ctypes.c_int] * 10 + [P(ctypes.c_int), P(ctypes.c_int), ctypes.c_long]
     L.roms_gpu_halo_map.restype = ctypes.c_long
@@ -550,6 +551,16 @@ class Model:
         r = self.L.roms_gpu_column_path()
         self._chk(min(r, 0), "column_path")
         return bool(r & 1), bool(r & 2)
+
+    def horizontal_path(self):
+        """The horizontal paths of this rank (roms_gpu_horizontal_path), from
+        the host functions the launchers call: {"edges": the fast step's
+        closed-edge mode, 0 none / 1 separate edge launches / 2 folded into
+        k_s2d_fb; "strips": (strips per row, jA, jB) of whole-step prsgrd or
+        None when tiles run everywhere; "omega_seg": omega takes k_omega_seg}."""
+        out = (ctypes.c_int * 8)()
+        self._chk(self.L.roms_gpu_horizontal_path(out), "horizontal_path")
+        return {"edges": out[0], "strips": (out[2], out[3], out[4]) if out[1] else None, "omega_seg": bool(out[5])}
 
     def halo_exchanges(self):
         """(exchanges in the last enqueued step, fast-loop exchange interval)
