@@ -321,8 +321,17 @@ int roms_gpu_column_path(void);
  *           the other rows of 1..Mm run in tiles);
  *   out[5]  1 if omega takes the segment form (k_omega_seg: 32 columns or
  *           more and N within the segment solvers' depth), 0: two-pass k_omega;
- *   out[6], out[7]  reserved, 0.
- * Negative before init.                                                      */
+ *   out[6]  the closed-edge modes the fast steps of the last enqueued whole
+ *           step took (eager or graph capture; plus those of any
+ *           roms_gpu_step2d call since): bit m set if some fast step ran
+ *           mode m of out[0]; 0 before the first step.  out[0] is the mode
+ *           on this rank's own bounds.  A multi-rank fast loop with an
+ *           exchange interval K > 1 (roms_gpu_halo_exchanges) widens each
+ *           fast step's bounds by 2(K-m) cells on every rank boundary and
+ *           decides the fold on the widened bounds, so a rank with an east
+ *           or a north wall and none opposite can take 1 and 2 in turn;
+ *   out[7]  reserved, 0.
+ * Negative before init.                                                   */
 int roms_gpu_horizontal_path(int out[8]);
 /* Self-test of the allocation path: `chunks` arrays of n doubles filled
  * with ones and freed, then allocated again through the library's

@@ -95,9 +95,10 @@ EXCHANGED = ("zeta", "ubar", "vbar", "u", "v", "t", "FlxU", "FlxV", "We", "Wi", 
 LMD_FIELDS = ("Akv", "Akt", "hbls", "hbbl", "ghat", "swr_frac")
 
 
-def check_decomposition(case, npx, npe, nsteps=5, fields=None):
+def check_decomposition(case, npx, npe, nsteps=5, fields=None, probe=None):
     """Every subdomain of an npx x npe run equals the single-domain run's
-    window bitwise (owned cells, and halos of the exchanged fields)."""
+    window bitwise (owned cells, and halos of the exchanged fields);
+    probe(model) runs on every rank after the steps (run_decomposed)."""
     per = case["case_id"] == 0
     if fields is None:
         fields = FIELDS + (LMD_FIELDS if case.get("lmd") else ())
@@ -105,7 +106,7 @@ def check_decomposition(case, npx, npe, nsteps=5, fields=None):
     m.step(nsteps)
     ref = {f: m.get(f) for f in fields}
     m.close()
-    parts, _ = run_decomposed(case, npx, npe, nsteps, fields=fields)
+    parts, _ = run_decomposed(case, npx, npe, nsteps, fields=fields, probe=probe)
     bad = []
     for rank, (iSW, jSW, Lm, Mm, got, _) in enumerate(parts):
         jn, inn = divmod(rank, npx)

@@ -502,15 +502,32 @@ int halo_setup(Halo& H, RomsComm* comm, const HaloPlan& plan, int maxlev, const 
     for (int d = 0; d < 8; d++) mxw = wide.g.cnt[d] > mxw ? wide.g.cnt[d] : mxw;
   // one slot of a message buffer holds the largest message of either plan
   H.cap = mx * (long)maxlev > mxw * (long)wide_maxlev ? mx * (long)maxlev : mxw * (long)wide_maxlev;
-  if (hipMalloc(&H.sbuf, (size_t)8 * H.cap * sizeof(double)) != hipSuccess ||
-      hipMalloc(&H.rbuf, (size_t)8 * H.cap * sizeof(double)) != hipSuccess ||
-      hipMalloc(&H.dred, (size_t)64 * (1 + (comm ? comm->nranks : 1)) * sizeof(double)) != hipSuccess) {
+  if (hipMalloc(&H.dred, (size_t)64 * (1 + (comm ? comm->nranks : 1)) * sizeof(double)) != hipSuccess) {
     err = "halo_setup: hipMalloc failed";
     return -2;
   }
   if (hipStreamCreateWithFlags(&H.cs, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&H.efork, hipEventDisableTiming) != hipSuccess) {
     err = "halo_setup: stream/event creation failed";
+    return -2;
+  }
+  if (comm && comm->nranks > 1) {
+    // ... of any rank: a neighbour's buffers are addressed slot by slot with
+    // this rank's cap (the in-process copies from its sbuf, the IPC writes
+    // into its rbuf2), and the ranks' largest messages differ when their
+    // extents or their sets of neighbours do (an uneven mpi_setup split, a
+    // rank with no wall beside ranks with one)
+    const double mine = (double)H.cap;
+    std::vector<double> all((size_t)comm->nranks);
+    if (halo_allgather(H, H.cs, &mine, 1, all.data()) != 0) {
+      err = "halo_setup: message-size allgather failed";
+      return -5;
+    }
+    for (double v : all) H.cap = (long)v > H.cap ? (long)v : H.cap;
+  }
+  if (hipMalloc(&H.sbuf, (size_t)8 * H.cap * sizeof(double)) != hipSuccess ||
+      hipMalloc(&H.rbuf, (size_t)8 * H.cap * sizeof(double)) != hipSuccess) {
+    err = "halo_setup: hipMalloc failed";
     return -2;
   }
   for (hipEvent_t& e : H.xev)

@@ -1039,6 +1039,14 @@ int s2d_edge_mode(const Dev& d) {
   return !closed ? 0 : (fold ? 2 : 1);
 }
 
+// one context per host thread, as the shim's (roms_shim.cpp Ctx)
+static thread_local int s2d_modes_mask = 0;
+int s2d_edge_modes_taken(bool reset) {
+  const int m = s2d_modes_mask;
+  if (reset) s2d_modes_mask = 0;
+  return m;
+}
+
 // one fast step's kernels over the bounds of d (launch_step2d): the fused
 // step (or the split form), then the open / closed edges
 void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& t) {
@@ -1046,6 +1054,7 @@ void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& 
   const bool closed = b.west_edge || b.east_edge || b.south_edge || b.north_edge;
   Range RB{b.istrR, b.iendR, b.jstrR, b.jendR};
   const int cmode = s2d_edge_mode(d);
+  s2d_modes_mask |= 1 << cmode;   // roms_gpu_horizontal_path out[6]
   const bool fold = cmode == 2;
   Halo* H = const_cast<Halo*>(d.halo);   // multi-rank exchange state (host bookkeeping)
   // single rank (no halo exchange object) with the fused kernel: periodic

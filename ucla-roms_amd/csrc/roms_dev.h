@@ -448,6 +448,10 @@ void setup_omega_seg();   // k_omega_seg<true>'s dynamic LDS limit
 // strips, their rows jA..jB and the strips per row (k_prsgrd.hip)
 bool omega_takes_seg(const Dev& d, int width);
 int s2d_edge_mode(const Dev& d);
+// bit m set: a fast step this host thread launched since the last `reset`
+// took closed-edge mode m (launch_fast_step, on the bounds a multi-rank fast
+// step widens: the mode can differ from one fast step to the next)
+int s2d_edge_modes_taken(bool reset = false);
 bool prsgrd_takes_strips(const Dev& d, bool with_uv, int& jA, int& jB, int& nstrip);
 double pre_step3d_dtau(const Dev& d, const Tlev& t);   // pre_step3d's dtau (k_pre_step3d.hip)
 void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx);

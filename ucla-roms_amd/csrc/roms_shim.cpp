@@ -428,6 +428,7 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   hipStream_t s = g.s;
   Tlev T = to_tlev(t);
   const long exch0 = g.halo.nexch;
+  (void)s2d_edge_modes_taken(true);   // the modes of this step's fast steps (roms_gpu_horizontal_path)
   const bool pot = g.cfg.pot_tides != 0;
   g.rho_slot = 0;
   // Two streams where the reference's order has no data dependence (single
@@ -756,6 +757,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   g.have_volume = false;
   g.area = g.volume = 0.0;
   g.d = Dev{};
+  (void)s2d_edge_modes_taken(true);
   {
     // device row pitch: Lm+4 rounded up to 128 B, base shifted so that i = 1
     // starts a line (roms_dev.h); ROMS_GPU_PITCH=0 keeps the host layout
@@ -1337,7 +1339,8 @@ int roms_gpu_horizontal_path(int out[8]) {
   out[3] = strips ? jA : 0;
   out[4] = strips ? jB : -1;
   out[5] = omega_takes_seg(d, d.b.iend - d.b.istr + 1) ? 1 : 0;
-  out[6] = out[7] = 0;
+  out[6] = s2d_edge_modes_taken();
+  out[7] = 0;
   return 0;
 }
 

@@ -562,6 +562,16 @@ class Model:
         self._chk(self.L.roms_gpu_horizontal_path(out), "horizontal_path")
         return {"edges": out[0], "strips": (out[2], out[3], out[4]) if out[1] else None, "omega_seg": bool(out[5])}
 
+    def fast_step_edge_modes(self):
+        """The set of closed-edge modes (0 / 1 / 2 as "edges" of
+        horizontal_path()) the fast steps of the last enqueued whole step
+        took (roms_gpu_horizontal_path out[6]); empty before the first step.
+        A multi-rank fast step decides the fold on the bounds it widens, so
+        the set can hold 1 and 2 where "edges" names one of them."""
+        out = (ctypes.c_int * 8)()
+        self._chk(self.L.roms_gpu_horizontal_path(out), "horizontal_path")
+        return {m for m in range(3) if out[6] >> m & 1}
+
     def halo_exchanges(self):
         """(exchanges in the last enqueued step, fast-loop exchange interval)
         -- roms_gpu_halo_exchanges."""
