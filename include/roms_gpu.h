@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 18
+#define ROMS_GPU_ABI_VERSION 19
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -308,6 +308,19 @@ int roms_gpu_s2d_window(void);
 #define ROMS_COLPATH_SEG 1
 #define ROMS_COLPATH_GLOBAL 2
 int roms_gpu_column_path(void);
+/* lmd_vmix leaves out work past the boundary layers; the fields are bitwise
+ * those of the full forms.  ROMS_GPU_KPP_LEAN (read at init) is a mask of the
+ * three parts, default 7, 0 for the full forms:
+ *   1  k_kpp_ext forms Vtsq (and loads the swr_frac that feeds it) only
+ *      until every column of the wavefront has its surface layer index kbls;
+ *   2  k_kpp_ext keeps FC(0:keep) of the bulk Richardson integral in LDS at
+ *      every N instead of the whole column FC(0:N) (in global scratch at
+ *      N >= 64); keep = ROMS_GPU_KPP_FCKEEP, 1..16, default 16.  A
+ *      wavefront with a bottom layer reaching above level keep repeats the
+ *      FC sweep for the levels above;
+ *   4  k_kpp_int's kbls scan stops at the first level outside the layer.
+ * Returns mask + 256 * keep of the live model, negative before init.       */
+int roms_gpu_kpp_lean(void);
 /* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
  * edges and the ROMS_GPU_* switches by the same host functions the launchers
  * call:

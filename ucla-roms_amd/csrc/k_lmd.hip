@@ -12,7 +12,8 @@
 //   k_kpp_ext  over the extended range (I_EXT_RANGE x J_EXT_RANGE): one
 //              descending sweep produces the raw gradient Richardson number
 //              Rig(1:N-1) (lmd_vmix.F:155-168), the bulk-Richardson integral
-//              FC(0:N) kept in LDS, the surface layer search kbls and hbl
+//              FC, of which only the lowest levels FC(0:keep) are kept (in
+//              LDS), the surface layer search kbls and hbl
 //              (lmd_kpp.F:200-275), then the bottom layer bbl (:276-305);
 //              alpha/beta, Bo, Bosol and ustar are stored for the second pass.
 //   k_kpp_int  over the interior: the masked isotropic smoothing of hbl/bbl
@@ -217,10 +218,24 @@ constexpr int kKblsG = ROMS_KBLS_G;
 constexpr int kKppPfd = ROMS_KPP_PFD;
 
 // ---- pass 1: extended range ----
+// Work past the boundary layers is left out (Params::kpp_lean, bitwise the
+// full form):
+//   bit 1  Cr(k) = FC(k) + Vtsq(k) only finds kbls, the first level from the
+//          top with Cr < 0: once every lane of the wavefront has its kbls,
+//          Vtsq (two sqrt, wscale_ws) and the swr_frac loads that feed it
+//          are no longer formed.  A lane whose Cr never turns negative keeps
+//          its wavefront sweeping to the bottom.
+//   KEEP   (bit 2) FC(0:N) is read back only by the bottom layer search, which
+//          walks up from k = 1 to the first Cr(k) = FC(k) - FC(0) > 0: only
+//          FC(0:keep) is kept, in an LDS slot of keep + 1 levels per wave, at
+//          every N (no global scratch column).  A wavefront with a lane whose
+//          bottom layer reaches above level keep repeats the descending FC
+//          sweep over k = N-1 .. keep+1 (same loads, same expression: the
+//          same FP64 sequence, so bitwise the FC(k) a full column would hold).
 #ifndef ROMS_KPP_EXT_WAVES
 #define ROMS_KPP_EXT_WAVES 3   // waves per SIMD the register budget is cut for (the next level in flight: 3)
 #endif
-template <class C>
+template <class C, bool KEEP = false>
 __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range E, int tind, int nstp, KppConst kc) {
   ROMS_IJC_OR_RETURN(E)
   const Bounds& b = d.b;
@@ -229,14 +244,17 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   const int N = b.N;
   const long n2 = b.n2, ij = IJ(b, i, j), sj = b.nx2;
   const double g = P.g, vonKar = P.vonKar, Ri_inv = 1. / kRicr;
-  // FC(0:N): the LDS column, or the global scratch column through the
-  // column's buffer offset (ColGlb: no 64-bit address per level)
+  // FC(0:keep) in the wave's LDS slot (KEEP), else FC(0:N): the LDS column,
+  // or the global scratch column through the column's buffer offset (ColGlb:
+  // no 64-bit address per level)
   const C FCc = ColMake<C>::at(d, 0, 0, ij);
   const BufF64 FCg(d.f.colscr);
   constexpr bool kGlb = std::is_same<C, ColGlb>::value;
-  auto fc_set = [&](int k, double v) {
+  static_assert(!KEEP || std::is_same<C, ColLds>::value, "KEEP: the LDS slot");
+  const int keep = KEEP ? (P.kpp_fckeep < N ? P.kpp_fckeep : N) : N;
+  auto fc_set = [&](int k, double v) {   // k wave-uniform
     if constexpr (kGlb) FCg.st(v, (unsigned)ij * 8u, (unsigned)k * (unsigned)n2 * 8u);
-    else FCc[k] = v;
+    else if (!KEEP || k <= keep) FCc[k] = v;
   };
   auto fc_get = [&](int k) {
     if constexpr (kGlb) return FCg.ld((unsigned)ij * 8u, (unsigned)k * (unsigned)n2 * 8u);
@@ -303,12 +321,26 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   // level k, z_w at w level k, sw and bvf at w level k-1 (its w level k
   // values are the level above's); the next level's are loaded before this
   // level's stores, so a level costs one memory round trip, not three
+  // (need_sw false: the swr_frac load is dropped -- kBufOff reads 0 without
+  // a memory access -- once no Vtsq will use it)
   struct Lv { double u0, u1, v0, v1, hz, zr, zw, swm, bm; };
-  auto ldlev = [&](int k, Lv& L) {
+  auto ldlev = [&](int k, Lv& L, bool need_sw) {
     const unsigned o = (unsigned)(k - 1) * lv, ow = (unsigned)k * lv;
     L.u0 = U.ld(vo, o); L.u1 = U.ld(vx, o); L.v0 = V.ld(vo, o); L.v1 = V.ld(vy, o);
     L.hz = Hz.ld(vo, o); L.zr = zr.ld(vo, o); L.zw = zw.ld(vo, ow);
-    L.swm = sw.ld(vo, o); L.bm = bvf.ld(vo, o);
+    L.swm = sw.ld(need_sw ? vo : kBufOff, o); L.bm = bvf.ld(vo, o);
+  };
+  // one level's term of the bulk Richardson integral (lmd_kpp.F:200-215):
+  // u, v, Hz at rho levels k+1 (p) and k, z_w and bvf at w level k
+  auto fc_term = [&](double u0p, double u1p, double v0p, double v1p, double hzp, double u0, double u1, double v0,
+                     double v1, double hz, double zwk, double bk) {
+    const double cu = zwN - zwk, cd = zwk - zw0;
+    const double cff_up = cu * cu, cff_dn = cd * cd;
+    const double Kern = cff_up * cff_dn / ((cff_up + eh2) * (cff_dn + eb2));
+    const double du = u0p + u1p - u0 - u1;
+    const double dv = v0p + v1p - v0 - v1;
+    const double hh = hz + hzp;
+    return Kern * (0.5 * (du * du + dv * dv) / hh - 0.5 * hh * (Ri_inv * bk + kC_Ek * ff * ff));
   };
   // k = N: FC(N) = 0, Cr(N) = Vtsq(N)
   const unsigned oN = (unsigned)(N - 1) * lv;
@@ -317,15 +349,20 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   double hzp = Hz.ld(vo, oN), zrp = zr.ld(vo, oN);
   double swc = sw.ld(vo, oN), bc = bvf.ld(vo, oN);   // sw, bvf at w level k (carried down)
   Lv cur{};
-  if (N - 1 >= 1) ldlev(N - 1, cur);
+  if (N - 1 >= 1) ldlev(N - 1, cur, true);
   double FCk = 0.;
   fc_set(N, 0.);
   double Crp = FCk + vtsq(zrp, sw.ld(vo, (unsigned)N * lv), swc, bc);
   int kbls = Crp < 0. ? N : 0;
   double cr_k = Crp, cr_kp = 0., zr_k = zrp, zr_kp = 0.;
+  // wave-uniform (lanes past the range have returned): every lane has its
+  // kbls, so Vtsq, Cr and the swr_frac loads below are dropped.  The loads
+  // run one level ahead: the flag is settled before the next level's go out.
+  const bool skipv = (P.kpp_lean & 1) != 0;
+  bool vdone = skipv && __all(kbls != 0);
   for (int k = N - 1; k >= 1; k--) {
     Lv nxt = cur;
-    if (k > 1) ldlev(k - 1, nxt);
+    if (k > 1) ldlev(k - 1, nxt, !vdone);
     const unsigned ow = (unsigned)k * lv;
     const double u0 = cur.u0, u1 = cur.u1, v0 = cur.v0, v1 = cur.v1;
     const double hz = cur.hz, zrk = cur.zr, zwk = cur.zw, bk = bc;
@@ -337,24 +374,20 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
       rig.st(bk / (kRi0 * dmax(dudz * dudz + dvdz * dvdz, 1.E-10)), vo, ow);
     }
     // bulk Richardson integral (lmd_kpp.F:200-215)
-    {
-      const double cu = zwN - zwk, cd = zwk - zw0;
-      const double cff_up = cu * cu, cff_dn = cd * cd;
-      const double Kern = cff_up * cff_dn / ((cff_up + eh2) * (cff_dn + eb2));
-      const double du = u0p + u1p - u0 - u1;
-      const double dv = v0p + v1p - v0 - v1;
-      const double hh = hz + hzp;
-      FCk = FCk + Kern * (0.5 * (du * du + dv * dv) / hh - 0.5 * hh * (Ri_inv * bk + kC_Ek * ff * ff));
-      fc_set(k, FCk);
+    FCk = FCk + fc_term(u0p, u1p, v0p, v1p, hzp, u0, u1, v0, v1, hz, zwk, bk);
+    fc_set(k, FCk);
+    if (!vdone) {
+      const double Cr = FCk + vtsq(zrk, swc, cur.swm, cur.bm);
+      if (kbls == 0 && Cr < 0.) {
+        kbls = k;
+        cr_k = Cr; cr_kp = Crp; zr_k = zrk; zr_kp = zrp;
+      }
+      Crp = Cr;
+      swc = cur.swm;
+      vdone = skipv && __all(kbls != 0);
     }
-    const double Cr = FCk + vtsq(zrk, swc, cur.swm, cur.bm);
-    if (kbls == 0 && Cr < 0.) {
-      kbls = k;
-      cr_k = Cr; cr_kp = Crp; zr_k = zrk; zr_kp = zrp;
-    }
-    Crp = Cr;
     u0p = u0; u1p = u1; v0p = v0; v1p = v1; hzp = hz; zrp = zrk;
-    swc = cur.swm; bc = cur.bm;
+    bc = cur.bm;
     cur = nxt;
   }
   // FC(0) (lmd_kpp.F:216-229): level-1 values are the carried ones, FCk is FC(1)
@@ -381,26 +414,52 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   const double FC0 = fc0;
   double bbl = zwN - zw0;
   // the first k upward with Cr(k) > 0 and Cr(k-1) (0 below k = 1): FC read
-  // kKblsG levels at a time, the scan ends once every lane of the wave has
-  // its level (one load per iteration waited on a round trip per level)
+  // kKblsG levels at a time (up to level keep: N unless KEEP), the scan ends
+  // once every lane of the wave has its level (one load per iteration waited
+  // on a round trip per level)
   int kb = 0;
   double crk = 0., crmk = 0.;
   {
     constexpr int G = kKblsG;
     double crm = 0.;
-    for (int k0 = 1; k0 <= N; k0 += G) {   // k0 wave-uniform
+    for (int k0 = 1; k0 <= keep; k0 += G) {   // k0 wave-uniform
       double c[G];
 #pragma unroll
-      for (int q = 0; q < G; q++) c[q] = fc_get(k0 + q <= N ? k0 + q : N);
+      for (int q = 0; q < G; q++) c[q] = fc_get(k0 + q <= keep ? k0 + q : keep);
 #pragma unroll
       for (int q = 0; q < G; q++) {
-        if (kb == 0 && k0 + q <= N) {
+        if (kb == 0 && k0 + q <= keep) {
           const double cr = c[q] - FC0;
           if (cr > 0.) { kb = k0 + q; crk = cr; crmk = crm; }
           crm = cr;
         }
       }
       if (__all(kb != 0)) break;
+    }
+  }
+  if constexpr (KEEP) {
+    // some lane's bottom layer reaches above level keep (wave-uniform test):
+    // FC(N-1 .. keep+1) once more, top down as in the first sweep, with no
+    // Rig store and no Vtsq.  Cr(k+1) is judged when Cr(k) is known, and a
+    // lower level replaces a higher one, so lanes without a level yet end
+    // with the lowest k > keep that has Cr(k) > 0, its Cr(k) and Cr(k-1).
+    if (keep < N && !__all(kb != 0)) {
+      double u0p = U.ld(vo, oN), u1p = U.ld(vx, oN), v0p = V.ld(vo, oN), v1p = V.ld(vy, oN), hzp = Hz.ld(vo, oN);
+      double FCf = 0.;
+      double crp = 0. - FC0;   // Cr(N): FC(N) = 0
+      int kf = 0;
+      double crkf = 0., crmf = 0.;
+      for (int k = N - 1; k > keep; k--) {
+        const unsigned o = (unsigned)(k - 1) * lv, ow = (unsigned)k * lv;
+        const double u0 = U.ld(vo, o), u1 = U.ld(vx, o), v0 = V.ld(vo, o), v1 = V.ld(vy, o), hz = Hz.ld(vo, o);
+        FCf = FCf + fc_term(u0p, u1p, v0p, v1p, hzp, u0, u1, v0, v1, hz, zw.ld(vo, ow), bvf.ld(vo, ow));
+        const double cr = FCf - FC0;
+        if (crp > 0.) { kf = k + 1; crkf = crp; crmf = cr; }
+        crp = cr;
+        u0p = u0; u1p = u1; v0p = v0; v1p = v1; hzp = hz;
+      }
+      if (crp > 0.) { kf = keep + 1; crkf = crp; crmf = fc_get(keep) - FC0; }   // Cr(keep) from the slot
+      if (kb == 0 && kf != 0) { kb = kf; crk = crkf; crmk = crmf; }
     }
   }
   if (kb == 1) bbl = zr.ld(vo, 0) - zw0;
@@ -460,16 +519,26 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
   // (the downward scan keeps its last hit: kbls is the smallest k in 1..N-1
   // with z_w(k) > zwN - hbl, else N).  Levels are loaded kKblsG at a time --
   // a scan with one load per iteration waited on 99 round trips per column.
+  // z_w increases with k (Hz > 0: set_depth), so the levels that pass are the
+  // top ones and the last hit is the level above the first that fails: the
+  // scan ends (Params::kpp_lean bit 4) once every lane of the wave has seen a
+  // level fail, with the kbls the full scan would keep.
   int kbls = N;
   {
     constexpr int G = kKblsG;
+    const bool early = (P.kpp_lean & 4) != 0;
+    bool below = false;   // a level of this lane failed
     for (int k0 = N - 1; k0 >= 1; k0 -= G) {   // k0 wave-uniform: scalar level offsets
       double z[G];
 #pragma unroll
       for (int q = 0; q < G; q++) z[q] = zw.ld(vo, (unsigned)(k0 - q >= 1 ? k0 - q : 1) * lv);
 #pragma unroll
       for (int q = 0; q < G; q++)
-        if (k0 - q >= 1 && z[q] > zwN - hbl) kbls = k0 - q;
+        if (k0 - q >= 1) {
+          if (z[q] > zwN - hbl) kbls = k0 - q;
+          else below = true;
+        }
+      if (early && __all(below)) break;
     }
   }
   const double Bo = F.lmd_Bo[ij], Bosol = F.lmd_Bosol[ij], ustar = F.lmd_ustar[ij];
@@ -695,7 +764,10 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
   kc.Cg = Cstar * vonKar * std::pow(c_s * vonKar * epssfc, 1. / 3.);
   kc.Vtc = Cv * std::sqrt(-betaT / (c_s * epssfc)) / (kRicr * (vonKar * vonKar));
   const int first = t.iic == t.forw_start;  // FIRST_TIME_STEP with EXACT_RESTART
-  if (d.f.colscr)
+  if (d.p.kpp_lean & 2)   // FC(0:keep) only, at every N
+    hipLaunchKernelGGL((k_kpp_ext<ColLds, true>), gridc_of(E), dim3(kCX),
+                       col_lds_bytes(1, d.p.kpp_fckeep < b.N ? d.p.kpp_fckeep : b.N), s, d, E, tind, t.nstp, kc);
+  else if (d.f.colscr)
     hipLaunchKernelGGL(k_kpp_ext<ColGlb>, gridc_of(E), dim3(kCX), 0, s, d, E, tind, t.nstp, kc);
   else
     hipLaunchKernelGGL(k_kpp_ext<ColLds>, gridc_of(E), dim3(kCX), col_lds_bytes(1, b.N), s, d, E, tind, t.nstp, kc);

@@ -94,6 +94,11 @@ struct Params {
   int nriv, nrivf;  // river_frc.F: number of rivers (0: river_source off), river faces
   int curvgrid;   // CURVGRID && UV_ADV: curvature terms (compute_horiz_rhs_uv_terms.h:8-11)
   int obc;        // open edges: 1 W, 2 E, 4 S, 8 N (Flather / Orlanski + *_FRC_BRY)
+  // (two shorts in the padding ahead of the doubles: Params keeps its size and every other member its offset)
+  short kpp_lean;   // lmd_vmix leaves out work past the boundary layers, bitwise (ROMS_GPU_KPP_LEAN bits, default 7, 0: the full forms):
+                    // 1 k_kpp_ext drops Vtsq and its swr_frac loads once the wave has its kbls, 2 k_kpp_ext keeps FC(0:kpp_fckeep) only,
+                    // 4 k_kpp_int's kbls scan ends at the first failing level
+  short kpp_fckeep; // levels FC(0:keep) of k_kpp_ext's LDS slot, 1..kKppFcKeepMax (ROMS_GPU_KPP_FCKEEP); above them the FC sweep is repeated
   double ubind;   // OBC binding velocity
   double dt, dtfast, g, rho0, vonKar, qp2, gamma2, hc;
   double rdrg, Zob, Tcoef, T0, Scoef, S0;
@@ -500,6 +505,7 @@ void launch_t3dbc(const Dev& d, hipStream_t s, const Tlev& t, int itrc);
 // out (device, 6 doubles): avzeta, KE, KE2b sums, Cu_adv, Cu_w, blow-up flag
 void launch_diag(const Dev& d, hipStream_t s, const Tlev& t, double* out);
 void launch_swr_frac(const Dev& d, hipStream_t s);
+constexpr int kKppFcKeepMax = 16;   // most levels above FC(0) in k_kpp_ext's LDS slot: 17 x 64 x 8 B = 8.7 KB per wave
 void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind);
 // ADV_ISONEUTRAL (k_iso.hip): prsgrd's corrector slopes (+ their exchange),
 // step3d_uv2's diff3u/diff3v/idRz over its flux-correction ranges and their

@@ -997,6 +997,18 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     if (e && (atoi(e) == 0 || atoi(e) == 2 || atoi(e) == 8 || atoi(e) == 43)) P.kpp_ty = atoi(e);
   }
   {
+    // lmd_vmix without the work past the boundary layers (bitwise; the bits
+    // in roms_dev.h); ROMS_GPU_KPP_LEAN=0 for the full forms, 1..7 for a
+    // subset of the three parts.  ROMS_GPU_KPP_FCKEEP=1..kKppFcKeepMax: levels
+    // above FC(0) that k_kpp_ext keeps in LDS
+    const char* e = getenv("ROMS_GPU_KPP_LEAN");
+    P.kpp_lean = 7;
+    if (e && e[0] >= '0' && e[0] <= '7' && e[1] == 0) P.kpp_lean = e[0] - '0';
+    const char* k = getenv("ROMS_GPU_KPP_FCKEEP");
+    P.kpp_fckeep = kKppFcKeepMax;
+    if (k && atoi(k) >= 1 && atoi(k) <= kKppFcKeepMax) P.kpp_fckeep = atoi(k);
+  }
+  {
     const char* e = getenv("ROMS_GPU_HOIST");
     P.hoist = !(e && e[0] == '0');
   }
@@ -1324,6 +1336,11 @@ int roms_gpu_s2d_window(void) {
 int roms_gpu_column_path(void) {
   REQUIRE_INIT_NOJOIN();
   return (g.d.p.colseg ? ROMS_COLPATH_SEG : 0) | (g.d.f.colscr ? ROMS_COLPATH_GLOBAL : 0);
+}
+
+int roms_gpu_kpp_lean(void) {
+  REQUIRE_INIT_NOJOIN();
+  return g.d.p.kpp_lean + 256 * g.d.p.kpp_fckeep;
 }
 
 int roms_gpu_horizontal_path(int out[8]) {

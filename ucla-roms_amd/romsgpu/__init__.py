@@ -545,6 +545,14 @@ class Model:
         buffer window (roms_gpu_s2d_window; ROMS_GPU_S2D_WIN=0: pointers)."""
         return bool(self.L.roms_gpu_s2d_window())
 
+    def kpp_lean(self):
+        """(mask, keep): the parts of lmd_vmix that leave out work past the
+        boundary layers (ROMS_GPU_KPP_LEAN) and the FC levels k_kpp_ext keeps
+        in LDS (ROMS_GPU_KPP_FCKEEP), as read at init (roms_gpu_kpp_lean)."""
+        r = self.L.roms_gpu_kpp_lean()
+        self._chk(min(r, 0), "kpp_lean")
+        return r % 256, r // 256
+
     def column_path(self):
         """(segment solvers on, column scratch in global memory) as chosen at
         init from N, ROMS_GPU_COLSEG and ROMS_GPU_COL_GLOBAL (roms_gpu_column_path)."""
