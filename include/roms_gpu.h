@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 19
+#define ROMS_GPU_ABI_VERSION 20
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -321,6 +321,26 @@ int roms_gpu_column_path(void);
  *   4  k_kpp_int's kbls scan stops at the first level outside the layer.
  * Returns mask + 256 * keep of the live model, negative before init.       */
 int roms_gpu_kpp_lean(void);
+/* Hz, z_r, z_w formed inside the kernels.  The three arrays are functions of
+ * the free surface set_depth used, h, hinv and the Cs tables; the kernels of
+ * ROMS_GPU_VGRID (read at init; a mask, default 11, 0 for the streaming forms)
+ * form a column's levels from those instead of streaming the arrays, with
+ * set_depth's own expressions, so every field keeps its bits:
+ *   1  k_rho_eos_split     2  k_kpp_ext     4  k_kpp_int     8  k_set_huv
+ * (k_kpp_int measured slower with it and is off by default).
+ * They do so only while the stored arrays are set_depth's own: every
+ * set_depth (roms_gpu_set_depth, roms_gpu_init_sequence, the last fast step)
+ * makes the grid valid; writing Hz, z_r, z_w, h, hinv, Cs_w or Cs_r from the
+ * host (roms_gpu_copy_in, roms_gpu_upload) makes it invalid, and every kernel
+ * streams the arrays again until the next set_depth -- a host that supplies
+ * its own Hz keeps the reference's semantics.
+ * roms_gpu_vgrid returns mask + 256 * valid, negative before init.
+ * roms_gpu_vgrid_check compares the stored z_w, z_r, Hz with the values formed
+ * from the kept surface as bit patterns, over set_depth's range and the
+ * exchanged or wrapped halos; out[0..2] = mismatches of z_w, z_r, Hz (all 0
+ * whenever the grid is valid).                                              */
+int roms_gpu_vgrid(void);
+int roms_gpu_vgrid_check(long out[3]);
 /* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
  * edges and the ROMS_GPU_* switches by the same host functions the launchers
  * call:

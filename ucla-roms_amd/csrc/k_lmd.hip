@@ -235,7 +235,10 @@ constexpr int kKppPfd = ROMS_KPP_PFD;
 #ifndef ROMS_KPP_EXT_WAVES
 #define ROMS_KPP_EXT_WAVES 3   // waves per SIMD the register budget is cut for (the next level in flight: 3)
 #endif
-template <class C, bool KEEP = false>
+//   VG     (Params::vg bit kVgKppExt) Hz, z_r, z_w of the column from VGrid
+//          (roms_dev.h) instead of the three streamed arrays; z_w(k) is
+//          carried down the levels.
+template <class C, bool KEEP = false, bool VG = false>
 __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range E, int tind, int nstp, KppConst kc) {
   ROMS_IJC_OR_RETURN(E)
   const Bounds& b = d.b;
@@ -305,7 +308,10 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   const unsigned vo = (unsigned)ij * 8u, vx = vo + 8u, vy = vo + (unsigned)sj * 8u, lv = (unsigned)n2 * 8u;
   const BufF64 U(F.u + (long)(tind - 1) * b.n3), V(F.v + (long)(tind - 1) * b.n3), Hz(F.Hz), zr(F.z_r), zw(F.z_w),
       bvf(F.bvf), sw(F.swr_frac), rig(F.lmd_rig);
-  const double zwN = zw.ld(vo, (unsigned)N * lv), zw0 = zw.ld(vo, 0);
+  VGrid vg{};
+  if constexpr (VG) vg = vg_column(d, ij);
+  const double zwN = VG ? vg.zw1(N) : zw.ld(vo, (unsigned)N * lv), zw0 = VG ? vg.zw0() : zw.ld(vo, 0);
+  double zwc = VG ? vg_zw(vg, N - 1) : 0.;   // VG: z_w(k) of the next level the sweep forms (k = N-1 .. 1)
   const double eh = kEpssfc * hbl0, eb = kEpssfc * bbl0;
   const double eh2 = eh * eh, eb2 = eb * eb;
 
@@ -327,7 +333,7 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   auto ldlev = [&](int k, Lv& L, bool need_sw) {
     const unsigned o = (unsigned)(k - 1) * lv, ow = (unsigned)k * lv;
     L.u0 = U.ld(vo, o); L.u1 = U.ld(vx, o); L.v0 = V.ld(vo, o); L.v1 = V.ld(vy, o);
-    L.hz = Hz.ld(vo, o); L.zr = zr.ld(vo, o); L.zw = zw.ld(vo, ow);
+    if constexpr (!VG) { L.hz = Hz.ld(vo, o); L.zr = zr.ld(vo, o); L.zw = zw.ld(vo, ow); }   // VG: formed at the level itself
     L.swm = sw.ld(need_sw ? vo : kBufOff, o); L.bm = bvf.ld(vo, o);
   };
   // one level's term of the bulk Richardson integral (lmd_kpp.F:200-215):
@@ -346,7 +352,7 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   const unsigned oN = (unsigned)(N - 1) * lv;
   double u0p = U.ld(vo, oN), u1p = U.ld(vx, oN);  // level k+1
   double v0p = V.ld(vo, oN), v1p = V.ld(vy, oN);
-  double hzp = Hz.ld(vo, oN), zrp = zr.ld(vo, oN);
+  double hzp = VG ? zwN - zwc : Hz.ld(vo, oN), zrp = VG ? vg.zr(N) : zr.ld(vo, oN);
   double swc = sw.ld(vo, oN), bc = bvf.ld(vo, oN);   // sw, bvf at w level k (carried down)
   Lv cur{};
   if (N - 1 >= 1) ldlev(N - 1, cur, true);
@@ -365,7 +371,15 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
     if (k > 1) ldlev(k - 1, nxt, !vdone);
     const unsigned ow = (unsigned)k * lv;
     const double u0 = cur.u0, u1 = cur.u1, v0 = cur.v0, v1 = cur.v1;
-    const double hz = cur.hz, zrk = cur.zr, zwk = cur.zw, bk = bc;
+    double hz, zrk, zwk;
+    if constexpr (VG) {
+      const double lo = vg_zw(vg, k - 1);
+      zwk = zwc; zrk = vg.zr(k); hz = zwc - lo;
+      zwc = lo;
+    } else {
+      hz = cur.hz; zrk = cur.zr; zwk = cur.zw;
+    }
+    const double bk = bc;
     // raw gradient Richardson number (lmd_vmix.F:157-165), LMD_RIMIX only
     if (P.lmd_rimix) {
       const double cff = 0.5 / (zrp - zrk);
@@ -404,7 +418,7 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   }
   double hbl;
   if (kbls > 0) {
-    if (kbls == N) hbl = zwN - zr.ld(vo, oN);
+    if (kbls == N) hbl = zwN - (VG ? vg.zr(N) : zr.ld(vo, oN));
     else hbl = zwN - (zr_k * cr_kp - zr_kp * cr_k) / (cr_kp - cr_k);
   } else {
     hbl = zwN - zw0;
@@ -444,15 +458,25 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
     // lower level replaces a higher one, so lanes without a level yet end
     // with the lowest k > keep that has Cr(k) > 0, its Cr(k) and Cr(k-1).
     if (keep < N && !__all(kb != 0)) {
-      double u0p = U.ld(vo, oN), u1p = U.ld(vx, oN), v0p = V.ld(vo, oN), v1p = V.ld(vy, oN), hzp = Hz.ld(vo, oN);
+      double zwf = VG ? vg_zw(vg, N - 1) : 0.;   // VG: z_w(k) of the level below the one held
+      double u0p = U.ld(vo, oN), u1p = U.ld(vx, oN), v0p = V.ld(vo, oN), v1p = V.ld(vy, oN),
+             hzp = VG ? zwN - zwf : Hz.ld(vo, oN);
       double FCf = 0.;
       double crp = 0. - FC0;   // Cr(N): FC(N) = 0
       int kf = 0;
       double crkf = 0., crmf = 0.;
       for (int k = N - 1; k > keep; k--) {
         const unsigned o = (unsigned)(k - 1) * lv, ow = (unsigned)k * lv;
-        const double u0 = U.ld(vo, o), u1 = U.ld(vx, o), v0 = V.ld(vo, o), v1 = V.ld(vy, o), hz = Hz.ld(vo, o);
-        FCf = FCf + fc_term(u0p, u1p, v0p, v1p, hzp, u0, u1, v0, v1, hz, zw.ld(vo, ow), bvf.ld(vo, ow));
+        const double u0 = U.ld(vo, o), u1 = U.ld(vx, o), v0 = V.ld(vo, o), v1 = V.ld(vy, o);
+        double hz, zwk;
+        if constexpr (VG) {
+          const double lo = vg_zw(vg, k - 1);
+          zwk = zwf; hz = zwf - lo;
+          zwf = lo;
+        } else {
+          hz = Hz.ld(vo, o); zwk = zw.ld(vo, ow);
+        }
+        FCf = FCf + fc_term(u0p, u1p, v0p, v1p, hzp, u0, u1, v0, v1, hz, zwk, bvf.ld(vo, ow));
         const double cr = FCf - FC0;
         if (crp > 0.) { kf = k + 1; crkf = crp; crmf = cr; }
         crp = cr;
@@ -462,9 +486,10 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
       if (kb == 0 && kf != 0) { kb = kf; crk = crkf; crmk = crmf; }
     }
   }
-  if (kb == 1) bbl = zr.ld(vo, 0) - zw0;
-  else if (kb > 1) {   // per-lane level: VGPR offsets
-    const double zrm = zr.ld(vo + (unsigned)(kb - 2) * lv, 0u), zrk = zr.ld(vo + (unsigned)(kb - 1) * lv, 0u);
+  if (kb == 1) bbl = (VG ? vg.zr(1) : zr.ld(vo, 0)) - zw0;
+  else if (kb > 1) {   // per-lane level: VGPR offsets (VG: per-lane reads of the Cs_r table)
+    const double zrm = VG ? vg.zr(kb - 1) : zr.ld(vo + (unsigned)(kb - 2) * lv, 0u),
+                 zrk = VG ? vg.zr(kb) : zr.ld(vo + (unsigned)(kb - 1) * lv, 0u);
     bbl = (zrm * crk - zrk * crmk) / (crk - crmk) - zw0;
   }
   F.lmd_bbl[ij] = bbl * rm;
@@ -477,7 +502,9 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
 // the edges like load3x3) in LDS once, double-buffered with one barrier per
 // level, instead of nine global loads per lane; lanes past the range walk
 // the levels too (barriers) and store nothing.  Same values bitwise.
-template <bool kDD, int TY = 0, int MW = 1>   // MW: minimum waves per SIMD (VGPR cap)
+// VG (Params::vg bit kVgKppInt): z_w from VGrid -- the kbls scan, the levels'
+// z_w, z_w(N), z_w(0), the per-lane z_w at kbls and Hz(1).
+template <bool kDD, int TY = 0, int MW = 1, bool VG = false>   // MW: minimum waves per SIMD (VGPR cap)
 __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, Range R, EdgeClamp ec, int tind, int nstp,
                                                                    int first, KppConst kc) {
   constexpr bool STG = TY > 0;
@@ -514,7 +541,9 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
   // buffer accesses: the column in one VGPR offset, the level in an SGPR
   const unsigned vo = (unsigned)ij * 8u, lv = (unsigned)n2 * 8u;
   const BufF64 zw(F.z_w), sw(F.swr_frac);
-  const double zwN = zw.ld(vo, (unsigned)N * lv), zw0 = zw.ld(vo, 0);
+  VGrid vg{};
+  if constexpr (VG) vg = vg_column(d, ij);
+  const double zwN = VG ? vg.zw1(N) : zw.ld(vo, (unsigned)N * lv), zw0 = VG ? vg.zw0() : zw.ld(vo, 0);
   // kbls and the buoyancy forcing at the boundary-layer depth (lmd_kpp.F:348-372)
   // (the downward scan keeps its last hit: kbls is the smallest k in 1..N-1
   // with z_w(k) > zwN - hbl, else N).  Levels are loaded kKblsG at a time --
@@ -531,7 +560,8 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
     for (int k0 = N - 1; k0 >= 1; k0 -= G) {   // k0 wave-uniform: scalar level offsets
       double z[G];
 #pragma unroll
-      for (int q = 0; q < G; q++) z[q] = zw.ld(vo, (unsigned)(k0 - q >= 1 ? k0 - q : 1) * lv);
+      for (int q = 0; q < G; q++)
+        z[q] = VG ? vg.zw1(k0 - q >= 1 ? k0 - q : 1) : zw.ld(vo, (unsigned)(k0 - q >= 1 ? k0 - q : 1) * lv);
 #pragma unroll
       for (int q = 0; q < G; q++)
         if (k0 - q >= 1) {
@@ -549,7 +579,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
     // (an SGPR offset would be a loop over the wave's distinct values)
     const unsigned ok = vo + (unsigned)kbls * lv, om = vo + (unsigned)(kbls - 1) * lv;
     const double swm = sw.ld(om, 0u), swk = sw.ld(ok, 0u);
-    const double zwk = zw.ld(ok, 0u), zwm = zw.ld(om, 0u);
+    const double zwk = VG ? vg.zw1(kbls) : zw.ld(ok, 0u), zwm = VG ? vg_zw(vg, kbls - 1) : zw.ld(om, 0u);   // VG: per-lane Cs_w reads
     if (swm > 0.)
       Bfsfc = Bo + Bosol * (1. - swm * swk * (zwk - zwm) / (swk * (zwk - z_bl) + swm * (z_bl - zwm)));
     else
@@ -561,7 +591,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
     const long o = (long)(nstp - 1) * b.n3 + ij;
     const double u0 = F.u[o], u1 = F.u[o + 1], v0 = F.v[o], v1 = F.v[o + sj];
     wmb = vonKar * vonKar * sqrt(0.333333333333 * (u0 * u0 + u1 * u1 + u0 * u1 + v0 * v0 + v1 * v1 + v0 * v1)) /
-          log(1. + 0.5 * F.Hz[ij] / Zob);
+          log(1. + 0.5 * (VG ? vg.zw1(1) - zw0 : F.Hz[ij]) / Zob);
   }
   const double wsb = wmb;
 
@@ -585,7 +615,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
   constexpr bool dd = kDD;
   const double* __restrict__ Tt = F.t + (long)(tind - 1) * b.n3 + ij;
   const double* __restrict__ St = Tt + 3 * b.n3;
-  struct RL { double r[3][3]; double zw, t0, t1, s0, s1; double win[STG ? WQ : 1]; int k; };
+  struct RL { double r[3][3]; double zw, t0, t1, s0, s1; double win[STG ? WQ : 1]; int k; };   // zw (VG): Cs_w[k]
   auto rload = [&](int k, RL& L) {
     L.k = k;
     if (STG) {   // this thread's entries of the level's window (rimix is on)
@@ -594,13 +624,13 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
     } else if (rimix) {
       load3x3(b, ec, rig + (long)k * n2, i, j, L.r);
     }
-    L.zw = zw.ld(vo, (unsigned)k * lv);
+    L.zw = VG ? F.Cs_w[k] : zw.ld(vo, (unsigned)k * lv);   // VG: rcomp forms z_w(k) from Cs_w[k]
     if (dd) {
       const long o = (long)(k - 1) * n2;
       L.t0 = Tt[o]; L.t1 = Tt[o + n2]; L.s0 = St[o]; L.s1 = St[o + n2];
     }
   };
-  auto rcomp = [&](const RL& L, double& kv, double& kt, double& ks) {
+  auto rcomp = [&](const RL& L, double& kv, double& kt, double& ks, double& zwl) {   // zwl: z_w of the level
     if (rimix) {
       double Rig;
       if (STG) {
@@ -634,8 +664,8 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       kt = kNuws;
     }
     ks = kt;
-    if (dd) ddmix(L.t0, L.t1, L.s0, L.s1, L.zw, kt, ks);
-    const double zwk = L.zw;
+    const double zwk = VG ? vg.zw1(L.k, L.zw) : L.zw;
+    if (dd) ddmix(L.t0, L.t1, L.s0, L.s1, zwk, kt, ks);
     const double dist = zwk - zw0;
     if (dist < kLturb) {
       const double mult = sin(0.5 * kPi * (zwk - zw0) / kLturb);
@@ -643,6 +673,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       kt = kt * mult;
       ks = ks * mult;
     }
+    zwl = zwk;
   };
   const BufF64 Akv(F.Akv), AktT(F.Akt), AktS(F.Akt + b.n3w), ghat(F.ghat);
   const unsigned vs = act ? vo : kBufOff;   // lanes past the range store nothing
@@ -695,8 +726,8 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
 #pragma unroll
   for (int q = 0; q < PD; q++)
     if (N - 1 >= 2 + q) rload(2 + q, Lr[q]);
-  rcomp(La, rv, rt, rs);
-  double zk = La.zw;  // z_w of level k
+  double zk;  // z_w of level k
+  rcomp(La, rv, rt, rs, zk);
   double rvN = rv, rtN = rt, rsN = rs;  // raw level N-1 (known once reached)
   double sv = rv + akv, st = rt + akt, ss = rs + aks;  // level 0 (padded)
   finish(0, sv, st, ss, zw0);
@@ -708,8 +739,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
 #pragma unroll
       for (int q = 0; q + 1 < PD; q++) Lr[q] = Lr[q + 1];
       if (k + 1 + PD <= N - 1) rload(k + 1 + PD, Lr[PD - 1]);
-      rcomp(cur, rvn, rtn, rsn);
-      zk1 = cur.zw;
+      rcomp(cur, rvn, rtn, rsn, zk1);
       nv = rvn; nt = rtn; ns = rsn;
     } else {
       rvN = rv; rtN = rt; rsN = rs;
@@ -764,33 +794,41 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
   kc.Cg = Cstar * vonKar * std::pow(c_s * vonKar * epssfc, 1. / 3.);
   kc.Vtc = Cv * std::sqrt(-betaT / (c_s * epssfc)) / (kRicr * (vonKar * vonKar));
   const int first = t.iic == t.forw_start;  // FIRST_TIME_STEP with EXACT_RESTART
+  const bool vge = (d.p.vg & kVgKppExt) != 0, vgi = (d.p.vg & kVgKppInt) != 0;
+#define KPP_EXT(C, KEEP, lds)                                                                                       \
+  do {                                                                                                              \
+    if (vge) hipLaunchKernelGGL((k_kpp_ext<C, KEEP, true>), gridc_of(E), dim3(kCX), lds, s, d, E, tind, t.nstp, kc); \
+    else hipLaunchKernelGGL((k_kpp_ext<C, KEEP, false>), gridc_of(E), dim3(kCX), lds, s, d, E, tind, t.nstp, kc);   \
+  } while (0)
   if (d.p.kpp_lean & 2)   // FC(0:keep) only, at every N
-    hipLaunchKernelGGL((k_kpp_ext<ColLds, true>), gridc_of(E), dim3(kCX),
-                       col_lds_bytes(1, d.p.kpp_fckeep < b.N ? d.p.kpp_fckeep : b.N), s, d, E, tind, t.nstp, kc);
+    KPP_EXT(ColLds, true, col_lds_bytes(1, d.p.kpp_fckeep < b.N ? d.p.kpp_fckeep : b.N));
   else if (d.f.colscr)
-    hipLaunchKernelGGL(k_kpp_ext<ColGlb>, gridc_of(E), dim3(kCX), 0, s, d, E, tind, t.nstp, kc);
+    KPP_EXT(ColGlb, false, 0);
   else
-    hipLaunchKernelGGL(k_kpp_ext<ColLds>, gridc_of(E), dim3(kCX), col_lds_bytes(1, b.N), s, d, E, tind, t.nstp, kc);
+    KPP_EXT(ColLds, false, col_lds_bytes(1, b.N));
+#undef KPP_EXT
+#define KPP_INT(DD, TY, MW, grid, block)                                                                              \
+  do {                                                                                                                \
+    if (vgi) hipLaunchKernelGGL((k_kpp_int<DD, TY, MW, true>), grid, block, 0, s, d, R, ec, tind, t.nstp, first, kc);  \
+    else hipLaunchKernelGGL((k_kpp_int<DD, TY, MW, false>), grid, block, 0, s, d, R, ec, tind, t.nstp, first, kc);     \
+  } while (0)
+  const EdgeClamp ec = edge_clamp(b);
   if (d.p.kpp_ty && d.p.lmd_rimix) {   // staged Rig windows on 64 x TY column blocks
     const int ty = d.p.lmd_ddmix ? 4 : (d.p.kpp_ty == 8 || d.p.kpp_ty == 2) ? d.p.kpp_ty : 4;   // the DDMIX form is instantiated on 64x4 only
     dim3 g = gridc_of(R);
     g.y = (g.y + ty - 1) / ty;
-    const EdgeClamp ec = edge_clamp(b);
-    if (d.p.lmd_ddmix)
-      hipLaunchKernelGGL((k_kpp_int<true, 4>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
-    else if (d.p.kpp_ty == 2)
-      hipLaunchKernelGGL((k_kpp_int<false, 2>), g, dim3(kCX, 2), 0, s, d, R, ec, tind, t.nstp, first, kc);
-    else if (d.p.kpp_ty == 8)
-      hipLaunchKernelGGL((k_kpp_int<false, 8>), g, dim3(kCX, 8), 0, s, d, R, ec, tind, t.nstp, first, kc);
-    else if (d.p.kpp_ty == 43)
-      hipLaunchKernelGGL((k_kpp_int<false, 4, 3>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
-    else
-      hipLaunchKernelGGL((k_kpp_int<false, 4>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
+    if (d.p.lmd_ddmix) KPP_INT(true, 4, 1, g, dim3(kCX, 4));
+    else if (d.p.kpp_ty == 2) KPP_INT(false, 2, 1, g, dim3(kCX, 2));
+    else if (d.p.kpp_ty == 8) KPP_INT(false, 8, 1, g, dim3(kCX, 8));
+    else if (d.p.kpp_ty == 43)   // the 3 waves/SIMD form spills: it keeps the streamed z_w
+      hipLaunchKernelGGL((k_kpp_int<false, 4, 3, false>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
+    else KPP_INT(false, 4, 1, g, dim3(kCX, 4));
   } else if (d.p.lmd_ddmix) {
-    hipLaunchKernelGGL(k_kpp_int<true>, gridc_of(R), dim3(kCX), 0, s, d, R, edge_clamp(b), tind, t.nstp, first, kc);
+    KPP_INT(true, 0, 1, gridc_of(R), dim3(kCX));
   } else {
-    hipLaunchKernelGGL(k_kpp_int<false>, gridc_of(R), dim3(kCX), 0, s, d, R, edge_clamp(b), tind, t.nstp, first, kc);
+    KPP_INT(false, 0, 1, gridc_of(R), dim3(kCX));
   }
+#undef KPP_INT
   // lmd_kpp.F:631-649: Akv, hbls, hbbl, Akt(itemp), Akt(isalt)
   ExchList L{};
   L.p[0] = d.f.Akv; L.nlev[0] = b.N + 1;

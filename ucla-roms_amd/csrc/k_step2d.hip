@@ -993,8 +993,8 @@ void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1,
     // time slots once at its end (the same values the per-step wraps give),
     // in one launch with set_depth's z_w, z_r, Hz (set_depth reads no zeta halo)
     if (t.iif == t.nfast)
-      launch_exchange_list(d, s, ExchList{{d.f.zeta, d.f.ubar, d.f.vbar, d.f.z_w, d.f.z_r, d.f.Hz},
-                                          {4, 4, 4, b.N + 1, b.N, b.N}, 6});
+      launch_exchange_list(d, s, ExchList{{d.f.zeta, d.f.ubar, d.f.vbar, d.f.z_w, d.f.z_r, d.f.Hz, d.f.z_sd},
+                                          {4, 4, 4, b.N + 1, b.N, b.N, 1}, 7});
     return;
   }
   if (K > 1) {

@@ -32,9 +32,8 @@ __global__ void __launch_bounds__(256) k_set_depth(Dev d, Range R, int iic, int 
                       F.dm_v[ij] * (F.vbar[IJL(b, i, j, 1)]);
   }
   const int N = b.N;
-  const double hc = d.p.hc, ds = 1.0 / (double)N;
   const double hh = F.h[ij];
-  const double hi = iic == 0 ? 1.0 / (hh + hc) : F.hinv[ij];
+  const double hi = iic == 0 ? 1.0 / (hh + d.p.hc) : F.hinv[ij];
   double z;
   if (last) {
     z = F.Zt_avg1[ij];
@@ -42,13 +41,16 @@ __global__ void __launch_bounds__(256) k_set_depth(Dev d, Range R, int iic, int 
   } else {
     z = F.zeta[IJL(b, i, j, knew)];
   }
-  double zw_prev = -hh;
+  // the levels through VGrid (roms_dev.h), the one definition the kernels
+  // that form the grid themselves share; z_sd keeps the z used here
+  // (zeta(knew) is overwritten by the next fast loop)
+  const VGrid vg = vg_make(d, z, hh, hi);
+  F.z_sd[ij] = z;
+  double zw_prev = vg.zw0();
   F.z_w[ij] = zw_prev;
   for (int k = 1; k <= N; k++) {
-    const double cff_w = hc * ds * (double)(k - N);
-    const double cff_r = hc * ds * ((double)(k - N) - 0.5);
-    const double zw = z + (z + hh) * (cff_w + F.Cs_w[k] * hh) * hi;
-    const double zr = z + (z + hh) * (cff_r + F.Cs_r[k] * hh) * hi;
+    const double zw = vg.zw1(k);
+    const double zr = vg.zr(k);
     F.z_w[ij + (long)k * b.n2] = zw;
     F.z_r[ij + (long)(k - 1) * b.n2] = zr;
     F.Hz[ij + (long)(k - 1) * b.n2] = zw - zw_prev;
@@ -56,17 +58,51 @@ __global__ void __launch_bounds__(256) k_set_depth(Dev d, Range R, int iic, int 
   }
 }
 
+// roms_gpu_vgrid_check: the stored z_w, z_r, Hz against VGrid's values from
+// z_sd, h, hinv as bit patterns, over set_depth's range plus the exchanged or
+// wrapped halos (R: the extended range); cnt[0..2] += mismatches of z_w, z_r, Hz
+__global__ void __launch_bounds__(256) k_vgrid_check(Dev d, Range R, unsigned long long* cnt) {
+  ROMS_IJ_OR_RETURN(R)
+  const Bounds& b = d.b;
+  const Fields& F = d.f;
+  const long ij = IJ(b, i, j);
+  const VGrid vg = vg_column(d, ij);
+  auto differ = [](double a, double c) { return __builtin_bit_cast(long long, a) != __builtin_bit_cast(long long, c); };
+  unsigned nw = 0, nr = 0, nh = 0;
+  double zw_prev = vg.zw0();
+  nw += differ(F.z_w[ij], zw_prev);
+  for (int k = 1; k <= b.N; k++) {
+    const double zw = vg.zw1(k);
+    nw += differ(F.z_w[ij + (long)k * b.n2], zw);
+    nr += differ(F.z_r[ij + (long)(k - 1) * b.n2], vg.zr(k));
+    nh += differ(F.Hz[ij + (long)(k - 1) * b.n2], zw - zw_prev);
+    zw_prev = zw;
+  }
+  if (nw) atomicAdd(cnt, (unsigned long long)nw);
+  if (nr) atomicAdd(cnt + 1, (unsigned long long)nr);
+  if (nh) atomicAdd(cnt + 2, (unsigned long long)nh);
+}
+void launch_vgrid_check(const Dev& d, hipStream_t s, unsigned long long* cnt) {
+  const Bounds& b = d.b;
+  const Range R{b.istrE, b.iendE, b.jstrE, b.jendE};
+  hipLaunchKernelGGL(k_vgrid_check, grid_of(R), dim3(kBX, kBY), 0, s, d, R, cnt);
+}
+
 void launch_set_depth(const Dev& d, hipStream_t s, const Tlev& t, bool exchange, bool last) {
   const Bounds& b = d.b;
   Range R{b.istrR, b.iendR, b.jstrR, b.jendR};
   hipLaunchKernelGGL(k_set_depth, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.iic, t.knew, (int)last);
   if (t.iic == 0) launch_exchange(d, s, d.f.hinv, 1);
-  if (exchange) launch_exchange_list(d, s, ExchList{{d.f.z_w, d.f.z_r, d.f.Hz}, {b.N + 1, b.N, b.N}, 3});
+  // z_sd travels with the arrays formed from it: wherever they have halo values, VGrid has their z
+  if (exchange) launch_exchange_list(d, s, ExchList{{d.f.z_w, d.f.z_r, d.f.Hz, d.f.z_sd}, {b.N + 1, b.N, b.N, 1}, 4});
 }
 
 // ---------------------------------------------------------------------------
 // set_HUV_tile (set_depth.F:190-234)
 // ---------------------------------------------------------------------------
+// VG (Params::vg bit kVgHuv): Hz of the column and of its i-1 / j-1
+// neighbours from VGrid, z_w(k) of each carried up the levels
+template <bool VG>
 __global__ void __launch_bounds__(256) k_set_huv(Dev d, Range R, int nrhs, int huv) {
   ROMS_IJ_OR_RETURN(R)
   const Bounds& b = d.b;
@@ -74,6 +110,35 @@ __global__ void __launch_bounds__(256) k_set_huv(Dev d, Range R, int nrhs, int h
   const bool du = i >= b.istr && i <= b.iendR && j >= b.jstrR && j <= b.jendR;
   const bool dv = i >= b.istrR && i <= b.iendR && j >= b.jstr && j <= b.jendR;
   const long ij = IJ(b, i, j), n2 = b.n2;
+  if constexpr (VG) {
+    const double dnu = du ? F.dn_u[ij] : 0.0, dmv = dv ? F.dm_v[ij] : 0.0;
+    const VGrid g0 = vg_column(d, ij), gx = vg_column(d, du ? ij - 1 : ij), gy = vg_column(d, dv ? ij - b.nx2 : ij);
+    const double* __restrict__ U = F.u + (long)(nrhs - 1) * b.n3 + ij;
+    const double* __restrict__ V = F.v + (long)(nrhs - 1) * b.n3 + ij;
+    double* __restrict__ FU = F.FlxU + ij;
+    double* __restrict__ FV = F.FlxV + ij;
+    double* __restrict__ HU = F.Hz_u + ij;
+    double* __restrict__ HV = F.Hz_v + ij;
+    double w0 = g0.zw0(), wx = gx.zw0(), wy = gy.zw0();   // z_w(k-1) of the three columns
+#pragma unroll 4
+    for (int k = 1; k <= b.N; k++) {
+      const long o = (long)(k - 1) * n2;
+      const double z0 = g0.zw1(k), zx = gx.zw1(k), zy = gy.zw1(k);
+      const double hz = z0 - w0;
+      if (du) {
+        const double hzm = zx - wx;
+        FU[o] = 0.5 * (hz + hzm) * dnu * (U[o]);
+        if (huv) HU[o] = 0.5 * (hz + hzm);
+      }
+      if (dv) {
+        const double hzm = zy - wy;
+        FV[o] = 0.5 * (hz + hzm) * dmv * (V[o]);
+        if (huv) HV[o] = 0.5 * (hz + hzm);
+      }
+      w0 = z0; wx = zx; wy = zy;
+    }
+    return;
+  }
   // one lane per column, all levels: dn_u/dm_v read once per column
   const double dnu = du ? F.dn_u[ij] : 0.0, dmv = dv ? F.dm_v[ij] : 0.0;
   const double* __restrict__ Hz = F.Hz + ij;
@@ -106,7 +171,10 @@ void launch_set_huv(const Dev& d, hipStream_t s, const Tlev& t, bool store_huv) 
   launch_rim_first(
       d, s, R, ExchList{{d.f.FlxU, d.f.FlxV}, {b.N, b.N}, 2},
       [&](const Range& r) {
-        hipLaunchKernelGGL(k_set_huv, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nrhs, (int)store_huv);
+        if (d.p.vg & kVgHuv)
+          hipLaunchKernelGGL(k_set_huv<true>, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nrhs, (int)store_huv);
+        else
+          hipLaunchKernelGGL(k_set_huv<false>, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nrhs, (int)store_huv);
       },
       [] {});
 }
@@ -758,7 +826,9 @@ struct PColumn {
   }
   __device__ __forceinline__ void last() { iter(1, 0.0, 0.0, 0.0); }
 };
-__device__ __forceinline__ PColumn p_column(const Dev& d, int i, int j, long ij, bool split) {
+// have_zwN: z_w(N) comes from the caller (VGrid) instead of the stored array
+__device__ __forceinline__ PColumn p_column(const Dev& d, int i, int j, long ij, bool split, bool have_zwN = false,
+                                            double zwN = 0.0) {
   const Bounds& b = d.b;
   PColumn c;
   c.g = d.p.g; c.grho = d.p.g / d.p.rho0; c.HalfGRho = 0.5 * c.grho; c.qp2 = d.p.qp2;
@@ -767,7 +837,7 @@ __device__ __forceinline__ PColumn p_column(const Dev& d, int i, int j, long ij,
   const bool doP = i >= 0 && i <= b.Lm && j >= 0 && j <= b.Mm && i >= b.istrU - 1 && i <= b.iend;
   c.Pb = BufF64(d.f.P);
   c.vP = doP ? (unsigned)ij * 8u : kBufOff;
-  c.zwN = d.f.z_w[ij + (long)b.N * b.n2];
+  c.zwN = have_zwN ? zwN : d.f.z_w[ij + (long)b.N * b.n2];
   c.ptide = c.tides ? d.f.ptide[ij] : 0.0;
   return c;
 }
@@ -843,7 +913,10 @@ __global__ void __launch_bounds__(256) k_rho_eos_linear(Dev d, Range R, int tidx
 #ifndef ROMS_RHO_MINW   // minimum waves per SIMD of k_rho_eos_split (VGPR cap; A/B builds)
 #define ROMS_RHO_MINW 1
 #endif
-template <bool kP>
+// VG (Params::vg bit kVgRho): z_r, Hz and z_w(N), z_w(0) from VGrid -- the
+// z_r / Hz prefetch rings and P's z_w(N) load go; z_w(k) is carried down the
+// levels (Hz(k) = z_w(k) - z_w(k-1))
+template <bool kP, bool VG>
 __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Range R, int tidx) {
   ROMS_IJ_OR_RETURN(R)
   const Bounds& b = d.b;
@@ -875,29 +948,52 @@ __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Ran
   const double gr = P.g / rho0;
   double r1p = 0.0, q1p = 0.0, zrp = 0.0;  // level k+1
   double rhoA = 0.0, rhoS = 0.0, bvN1 = 0.0, bv1 = 0.0;
+  VGrid vg{};
+  double zw_up = 0.0, zwN = 0.0;   // VG: z_w(k) of the level being formed, z_w(N)
+  double cw_n = 0.0, cr_n = 0.0;   // VG: Cs_w[k-1], Cs_r[k] of the next level formed, read a level ahead
+  if constexpr (VG) {
+    vg = vg_column(d, ij);
+    zwN = zw_up = vg.zw1(N);
+    cw_n = F.Cs_w[N - 1]; cr_n = F.Cs_r[N];
+  }
   PColumn pc;
-  if constexpr (kP) pc = p_column(d, i, j, ij, true);
+  if constexpr (kP) pc = p_column(d, i, j, ij, true, VG, zwN);
   // the next levels' inputs are loaded before this level's stores (a ring
   // of ROMS_RHO_PF levels), so the stores -- counted with the loads by
   // vmcnt -- do not hold back the loads below them
   constexpr int PF = ROMS_RHO_PF;
-  double pT[PF], pS[PF], pZ[PF], pH[PF];
+  double pT[PF], pS[PF], pZ[VG ? 1 : PF], pH[VG ? 1 : PF];
 #pragma unroll
   for (int q = 0; q < PF; q++) {
     const unsigned o = (unsigned)max(N - 1 - q, 0) * lv;
-    pT[q] = T.ld(vo, o); pS[q] = Sa.ld(vo, o); pZ[q] = zr.ld(vo, o); pH[q] = Hz.ld(vo, o);
+    pT[q] = T.ld(vo, o); pS[q] = Sa.ld(vo, o);
+    if constexpr (!VG) { pZ[q] = zr.ld(vo, o); pH[q] = Hz.ld(vo, o); }
   }
 #pragma unroll ROMS_RHO_UNROLL
   for (int k = N; k >= 1; k--) {
     const unsigned o = (unsigned)(k - 1) * lv;
     Tt = pT[0];
     Ts = pS[0];
-    const double zrk = pZ[0], hz = pH[0];
+    double zrk, hz;
+    if constexpr (VG) {
+      const double cw = cw_n, cr = cr_n;
+      cw_n = F.Cs_w[max(k - 2, 0)]; cr_n = F.Cs_r[max(k - 1, 1)];
+      const double zw_dn = vg.zw(k - 1, cw);
+      zrk = vg.zr(k, cr);
+      hz = zw_up - zw_dn;
+      zw_up = zw_dn;
+    } else {
+      zrk = pZ[0]; hz = pH[0];
+    }
 #pragma unroll
-    for (int q = 0; q + 1 < PF; q++) { pT[q] = pT[q + 1]; pS[q] = pS[q + 1]; pZ[q] = pZ[q + 1]; pH[q] = pH[q + 1]; }
+    for (int q = 0; q + 1 < PF; q++) {
+      pT[q] = pT[q + 1]; pS[q] = pS[q + 1];
+      if constexpr (!VG) { pZ[q] = pZ[q + 1]; pH[q] = pH[q + 1]; }
+    }
     {
       const unsigned on = (unsigned)max(k - 1 - PF, 0) * lv;   // level k - PF (clamped; unused past the bottom)
-      pT[PF - 1] = T.ld(vo, on); pS[PF - 1] = Sa.ld(vo, on); pZ[PF - 1] = zr.ld(vo, on); pH[PF - 1] = Hz.ld(vo, on);
+      pT[PF - 1] = T.ld(vo, on); pS[PF - 1] = Sa.ld(vo, on);
+      if constexpr (!VG) { pZ[PF - 1] = zr.ld(vo, on); pH[PF - 1] = Hz.ld(vo, on); }
     }
     sqrtTs = sqrt(dmax(0.0, Ts));
     const double r1 = (dr00 + Tt * (r01 + Tt * (r02 + Tt * (r03 + Tt * (r04 + Tt * r05)))) +
@@ -934,7 +1030,7 @@ __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Ran
     bvf.st(bv1, vo, 0);
   }
   const double cff1 = 1.0 / rho0;
-  const double cff = 1.0 / (F.z_w[ij + (long)N * n2] - F.z_w[ij]);
+  const double cff = VG ? 1.0 / (zwN - vg.zw0()) : 1.0 / (F.z_w[ij + (long)N * n2] - F.z_w[ij]);
   F.rhoA[ij] = cff * cff1 * rhoA;
   F.rhoS[ij] = 2.0 * cff * cff * cff1 * rhoS;
 }
@@ -954,8 +1050,11 @@ void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx) {
   Range R{b.istrE, b.iendE, b.jstrE, b.jendE};
   const bool kp = p_in_rho(d);
   if (d.p.nonlin_eos) {
-    if (kp) hipLaunchKernelGGL(k_rho_eos_split<true>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
-    else hipLaunchKernelGGL(k_rho_eos_split<false>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
+    const bool vg = (d.p.vg & kVgRho) != 0;
+    if (kp && vg) hipLaunchKernelGGL((k_rho_eos_split<true, true>), grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
+    else if (kp) hipLaunchKernelGGL((k_rho_eos_split<true, false>), grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
+    else if (vg) hipLaunchKernelGGL((k_rho_eos_split<false, true>), grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
+    else hipLaunchKernelGGL((k_rho_eos_split<false, false>), grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
   } else {
     if (kp) hipLaunchKernelGGL(k_rho_eos_linear<true>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);
     else hipLaunchKernelGGL(k_rho_eos_linear<false>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, tidx);

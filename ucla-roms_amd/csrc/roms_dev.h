@@ -94,11 +94,14 @@ struct Params {
   int nriv, nrivf;  // river_frc.F: number of rivers (0: river_source off), river faces
   int curvgrid;   // CURVGRID && UV_ADV: curvature terms (compute_horiz_rhs_uv_terms.h:8-11)
   int obc;        // open edges: 1 W, 2 E, 4 S, 8 N (Flather / Orlanski + *_FRC_BRY)
-  // (two shorts in the padding ahead of the doubles: Params keeps its size and every other member its offset)
+  // (four shorts ahead of the doubles)
   short kpp_lean;   // lmd_vmix leaves out work past the boundary layers, bitwise (ROMS_GPU_KPP_LEAN bits, default 7, 0: the full forms):
                     // 1 k_kpp_ext drops Vtsq and its swr_frac loads once the wave has its kbls, 2 k_kpp_ext keeps FC(0:kpp_fckeep) only,
                     // 4 k_kpp_int's kbls scan ends at the first failing level
   short kpp_fckeep; // levels FC(0:keep) of k_kpp_ext's LDS slot, 1..kKppFcKeepMax (ROMS_GPU_KPP_FCKEEP); above them the FC sweep is repeated
+  short vgrid;      // kernels that form Hz, z_r, z_w of a column from z_sd, h, hinv (VGrid) instead of streaming the arrays, bitwise
+                    // (ROMS_GPU_VGRID bits, default 11, 0: the streaming forms): 1 k_rho_eos_split, 2 k_kpp_ext, 4 k_kpp_int, 8 k_set_huv
+  short vg;         // the bits of vgrid in force: vgrid while the stored arrays are set_depth's own (the shim's validity flag), else 0
   double ubind;   // OBC binding velocity
   double dt, dtfast, g, rho0, vonKar, qp2, gamma2, hc;
   double rdrg, Zob, Tcoef, T0, Scoef, S0;
@@ -115,6 +118,7 @@ struct Fields {
   // BULK_FRC inputs (rho points) and rho-point stresses (bulk_frc.F, surf_flux.F)
   double *uwnd, *vwnd, *tair, *qair, *prate, *swrad, *lwrad, *sustr_r, *svstr_r;
   double *Cs_w, *Cs_r;  // scoord.F (N+1)
+  double* z_sd;         // the free surface the last set_depth formed z_w, z_r, Hz from (VGrid; not an ABI field)
   // ocean vars
   double *zeta, *ubar, *vbar, *u, *v, *t;
   double *FlxU, *FlxV, *We, *Wi, *Hz, *Hz_u, *Hz_v, *z_r, *z_w;
@@ -209,6 +213,45 @@ __device__ __forceinline__ double fmin0(double a) { return a < 0.0 ? a : 0.0; }
 __device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
 __device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
 __device__ __forceinline__ int iclamp(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// ---- the vertical grid of one column (set_depth.F:16-186) ----
+// z_w, z_r, Hz are functions of the column's free surface z, h, hinv and the
+// per-level constants Cs_w, Cs_r, hc, N.  k_set_depth stores them through
+// these functions, and the kernels switched by Params::vg form them again from
+// z_sd (the z set_depth used), h and hinv instead of streaming the 3-D arrays:
+// the same expressions in the same order (-ffp-contract=off), so the same bits.
+constexpr int kVgRho = 1, kVgKppExt = 2, kVgKppInt = 4, kVgHuv = 8, kVgAll = 15;   // Params::vgrid bits
+constexpr int kVgDefault = kVgRho | kVgKppExt | kVgHuv;   // k_kpp_int measured slower with it (profiles/r8_vgrid_ab.txt)
+struct VGrid {
+  const double *Cs_w, *Cs_r;
+  double z, h, hinv, hc, ds;
+  int N;
+  __device__ __forceinline__ double zw0() const { return -h; }
+  // csw = Cs_w[k], csr = Cs_r[k]: a level walk reads them a level ahead (a
+  // scalar load per level waited on in place costs the walk its latency)
+  __device__ __forceinline__ double zw1(int k, double csw) const {   // z_w(k), k = 1..N
+    const double cff_w = hc * ds * (double)(k - N);
+    return z + (z + h) * (cff_w + csw * h) * hinv;
+  }
+  __device__ __forceinline__ double zr(int k, double csr) const {    // z_r(k), k = 1..N
+    const double cff_r = hc * ds * ((double)(k - N) - 0.5);
+    return z + (z + h) * (cff_r + csr * h) * hinv;
+  }
+  __device__ __forceinline__ double zw(int k, double csw) const { return k == 0 ? zw0() : zw1(k, csw); }   // k = 0..N
+  __device__ __forceinline__ double zw1(int k) const { return zw1(k, Cs_w[k]); }
+  __device__ __forceinline__ double zr(int k) const { return zr(k, Cs_r[k]); }
+};
+__device__ __forceinline__ double vg_zw(const VGrid& g, int k) { return k == 0 ? g.zw0() : g.zw1(k); }   // k = 0..N
+__device__ __forceinline__ double vg_zr(const VGrid& g, int k) { return g.zr(k); }
+// a level walk carries z_w(k) across levels instead (Hz(k) = z_w(k) - z_w(k-1))
+__device__ __forceinline__ double vg_hz(const VGrid& g, int k) { return g.zw1(k) - vg_zw(g, k - 1); }
+__device__ __forceinline__ VGrid vg_make(const Dev& d, double z, double h, double hinv) {
+  return VGrid{d.f.Cs_w, d.f.Cs_r, z, h, hinv, d.p.hc, 1.0 / (double)d.b.N, d.b.N};
+}
+// the column's z, h, hinv loaded once; the levels then cost the scalar Cs_w[k] / Cs_r[k] only
+__device__ __forceinline__ VGrid vg_column(const Dev& d, long ij) {
+  return vg_make(d, d.f.z_sd[ij], d.f.h[ij], d.f.hinv[ij]);
+}
 
 // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs
 // (MI355X_MICROARCH.md: blocks b and b+8 share an XCD and its L2), so with
@@ -440,6 +483,8 @@ inline size_t col_smem_bytes(const Dev& d, int nslots) {
 void launch_set_depth(const Dev& d, hipStream_t s, const Tlev& t, bool exchange = true, bool last = false);
 // store_huv: also Hz_u/Hz_v (set_depth.F:220,227), read only by extract_data.F
 void launch_set_huv(const Dev& d, hipStream_t s, const Tlev& t, bool store_huv = true);
+// cnt (device, 3 counters, zeroed by the caller): mismatches of the stored z_w, z_r, Hz against VGrid
+void launch_vgrid_check(const Dev& d, hipStream_t s, unsigned long long* cnt);
 void launch_set_huv1(const Dev& d, hipStream_t s, const Tlev& t);
 // hcff > 0: the predictor's call also forms pre_step3d's Hz_bak/Hz_fwd (c3/c2) of the
 // interior cells with 0.5*dtau = hcff; returns whether it did (k_vertical.hip)

@@ -61,6 +61,13 @@ struct Ctx {
   bool hzuv_env = false;
   bool hzuv_valid = true;
   bool rho_reuse = true;      // ROMS_GPU_RHO_REUSE=0 turns the skip off
+  // The stored Hz, z_r, z_w are what set_depth formed from z_sd, h, hinv and
+  // the Cs tables, so the kernels of Params::vgrid may form them again (VGrid,
+  // roms_dev.h) instead of streaming them: set by every set_depth, cleared
+  // when the host writes one of those arrays through any entry (vg_host_write)
+  // -- a host that brings its own Hz keeps the streaming forms.  Params::vg
+  // follows it (vg_set).
+  bool vgrid_valid = false;
   std::string err;
   // graph cache: key = (nstp, knew at step start)
   std::map<long, hipGraphExec_t> graphs;
@@ -135,6 +142,26 @@ int min_rank_extent(int LL, int np) {
     mn = len < mn ? len : mn;
   }
   return mn;
+}
+
+void drop_graphs() {   // captured graphs hold the old Params / pointers
+  for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
+  g.graphs.clear();
+}
+void vg_set(bool valid) {
+  g.vgrid_valid = valid;
+  g.d.p.vg = valid ? g.d.p.vgrid : (short)0;
+}
+// the host wrote field `id`: Hz, z_r, z_w, h, hinv or a Cs table ends VGrid's validity
+void vg_host_write(int id) {
+  if (id != ROMS_Hz && id != ROMS_z_r && id != ROMS_z_w && id != ROMS_h && id != ROMS_hinv && id != ROMS_Cs_w &&
+      id != ROMS_Cs_r)
+    return;
+  if (g.vgrid_valid && !g.graphs.empty()) {
+    (void)hipStreamSynchronize(g.s);
+    drop_graphs();
+  }
+  vg_set(false);
 }
 
 #define CHECK_HIP(x)                                                                  \
@@ -580,6 +607,7 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
     T = to_tlev(t);
     launch_step2d(d, s, T, g.w1, g.w2);
   }
+  vg_set(true);   // the last fast step ran set_depth: from here the step's kernels may form the grid (d is g.d)
   if (t2d) {
     (void)hipEventRecord(g.ev[g.nev + 1], s);
     g.nev += 2;
@@ -1009,6 +1037,16 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     if (k && atoi(k) >= 1 && atoi(k) <= kKppFcKeepMax) P.kpp_fckeep = atoi(k);
   }
   {
+    // Hz, z_r, z_w formed in the kernel from z_sd, h, hinv (VGrid, bitwise; the
+    // bits in roms_dev.h); ROMS_GPU_VGRID=0 for the streaming forms, 1..15 a
+    // set of kernels.  Default 11: k_kpp_int (bit 4) is slower with it
+    const char* e = getenv("ROMS_GPU_VGRID");
+    P.vgrid = kVgDefault;
+    if (e && e[0] >= '0' && e[0] <= '9' && atoi(e) >= 0 && atoi(e) <= kVgAll) P.vgrid = (short)atoi(e);
+    P.vg = 0;
+    g.vgrid_valid = false;
+  }
+  {
     const char* e = getenv("ROMS_GPU_HOIST");
     P.hoist = !(e && e[0] == '0');
   }
@@ -1114,7 +1152,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   {
     // one allocation for them (dev_alloc slices it); a subdomain whose 2-D
     // set passes 2 GiB allocates them one by one (and runs the pointer form)
-    long n = 10 * dev_alloc_size(b.n2);   // s0..s9
+    long n = 11 * dev_alloc_size(b.n2);   // s0..s9, z_sd
     for (int id = 0; id < ROMS_NFIELDS; id++)
       if (planar2d(id)) n += dev_alloc_size(field_count(id, b));
     if (n * 8 < 2147483648L - (1L << 20)) {
@@ -1134,6 +1172,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   double** s2[] = {&F.s0, &F.s1, &F.s2, &F.s3, &F.s4, &F.s5, &F.s6, &F.s7, &F.s8, &F.s9};
   for (double** q : s2)
     if (scratch(*q, b.n2)) return -2;
+  if (scratch(F.z_sd, b.n2)) return -2;
   g.arena_n = g.arena_used;   // nothing else is sliced from it
   for (int id = 0; id < ROMS_NFIELDS; id++)
     if (!planar2d(id) && field(id)) return -2;
@@ -1270,6 +1309,7 @@ static int xfer(int id, bool up) {
   if (!g.f[id].host) { g.err = "field not registered"; return -1; }
   if (!up && !hzuv_readable(id)) return -5;
   if (up && (id == ROMS_Hz_u || id == ROMS_Hz_v)) g.hzuv_valid = true;
+  if (up) vg_host_write(id);
   CHECK_HIP(up ? field_h2d(id, g.f[id].d, g.f[id].host) : field_d2h(id, g.f[id].host, g.f[id].d));
   return 0;
 }
@@ -1280,6 +1320,7 @@ int roms_gpu_copy_in(int id, const double* src, long count) {
   REQUIRE_INIT();
   if (id < 0 || id >= ROMS_NFIELDS || count != g.f[id].hcount) { g.err = "roms_gpu_copy_in: bad field/size"; return -1; }
   if (id == ROMS_Hz_u || id == ROMS_Hz_v) g.hzuv_valid = true;
+  vg_host_write(id);
   CHECK_HIP(field_h2d(id, g.f[id].d, src));
   return 0;
 }
@@ -1315,7 +1356,7 @@ ROUTINE(roms_gpu_visc3d, launch_visc3d(g.d, g.s, T))
 ROUTINE(roms_gpu_step3d_uv2, launch_step3d_uv2(g.d, g.s, T))
 ROUTINE(roms_gpu_step3d_t, launch_step3d_t(g.d, g.s, T))
 ROUTINE(roms_gpu_t3dmix, launch_t3dmix(g.d, g.s, T))
-ROUTINE(roms_gpu_set_depth, launch_set_depth(g.d, g.s, T))
+ROUTINE(roms_gpu_set_depth, (launch_set_depth(g.d, g.s, T), vg_set(true)))
 #undef ROUTINE
 
 int roms_gpu_halo_transport(void) {
@@ -1336,6 +1377,24 @@ int roms_gpu_s2d_window(void) {
 int roms_gpu_column_path(void) {
   REQUIRE_INIT_NOJOIN();
   return (g.d.p.colseg ? ROMS_COLPATH_SEG : 0) | (g.d.f.colscr ? ROMS_COLPATH_GLOBAL : 0);
+}
+
+int roms_gpu_vgrid(void) {
+  REQUIRE_INIT_NOJOIN();
+  return g.d.p.vgrid + (g.vgrid_valid ? 256 : 0);
+}
+
+int roms_gpu_vgrid_check(long out[3]) {
+  REQUIRE_INIT_RO();
+  if (!out) { g.err = "roms_gpu_vgrid_check: null argument"; return -1; }
+  unsigned long long* cnt = (unsigned long long*)shim_scratch_small(3);
+  if (!cnt) { g.err = "roms_gpu_vgrid_check: out of device memory"; return -2; }
+  CHECK_HIP(hipMemsetAsync(cnt, 0, 3 * sizeof(unsigned long long), g.s));
+  launch_vgrid_check(g.d, g.s, cnt);
+  unsigned long long h[3] = {0, 0, 0};
+  CHECK_HIP(copy_on(h, cnt, sizeof(h), hipMemcpyDeviceToHost, g.s));
+  for (int q = 0; q < 3; q++) out[q] = (long)h[q];
+  return post_launch();
 }
 
 int roms_gpu_kpp_lean(void) {
@@ -1373,6 +1432,7 @@ int roms_gpu_step2d(const roms_tlev* t) {
   REQUIRE_HALO_OK();
   const Tlev T = to_tlev(t);
   launch_step2d(g.d, g.s, T, g.w1, g.w2);
+  if (T.iif == T.nfast) vg_set(true);   // the last fast step ends with set_depth
   return post_launch();
 }
 
@@ -1454,10 +1514,6 @@ int roms_gpu_set_river_frc(int nriv, const double* riv_uflx, const double* riv_v
     return -1;
   }
   CHECK_HIP(hipStreamSynchronize(g.s));
-  auto drop_graphs = [&]() {   // captured graphs hold the old Params / pointers
-    for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
-    g.graphs.clear();
-  };
   if (nriv == 0) {
     if (g.d.p.nriv) drop_graphs();
     g.d.p.nriv = 0;
@@ -1580,7 +1636,10 @@ int roms_gpu_step(roms_tlev* t) {
     enqueue_step(t, rho_current, store_huv);
     return post_launch();
   }
-  const long key = (long)t->nstp * 16 + t->knew + (rho_current ? 256 : 0) + (store_huv ? 512 : 0);
+  // the grid's validity at entry decides the forms ahead of the step's own
+  // set_depth; the step leaves it valid either way
+  const long key = (long)t->nstp * 16 + t->knew + (rho_current ? 256 : 0) + (store_huv ? 512 : 0) +
+                   (g.vgrid_valid ? 1024 : 0);
   auto it = g.graphs.find(key);
   roms_tlev t0 = *t;
   if (it == g.graphs.end()) {
@@ -1597,6 +1656,7 @@ int roms_gpu_step(roms_tlev* t) {
   }
   // replay; advance the host-side indices exactly as enqueue_step would
   CHECK_HIP(hipGraphLaunch(it->second, g.s));
+  vg_set(true);   // the replayed step ran set_depth
   t->nrhs = 3;
   t->nnew = 3 - t->nstp;
   g.rho_slot = t->nnew;   // the replayed step ended with rho_eos(nnew)
@@ -1613,6 +1673,7 @@ int roms_gpu_init_sequence(roms_tlev* t) {
   REQUIRE_INIT();
   const Tlev T = to_tlev(t);
   launch_set_depth(g.d, g.s, T);
+  vg_set(true);
   // main.F:217-220 (zeta at rest): at initialisation only, not after a
   // restart read (get_init leaves iic = ntstart - 1 > 0)
   if (g.cfg.lmd_mixing && t->iic == 0) {

@@ -553,6 +553,22 @@ class Model:
         self._chk(min(r, 0), "kpp_lean")
         return r % 256, r // 256
 
+    def vgrid(self):
+        """(mask, valid): the kernels that form Hz, z_r, z_w themselves
+        (ROMS_GPU_VGRID, as read at init) and whether the stored arrays are
+        set_depth's own, so that they do (roms_gpu_vgrid)."""
+        r = self.L.roms_gpu_vgrid()
+        self._chk(min(r, 0), "vgrid")
+        return r % 256, bool(r // 256)
+
+    def vgrid_mismatch(self):
+        """(z_w, z_r, Hz): stored values that differ bitwise from the ones
+        formed from the kept free surface, h and hinv, over set_depth's range
+        and the halos (roms_gpu_vgrid_check)."""
+        out = (ctypes.c_long * 3)()
+        self._chk(self.L.roms_gpu_vgrid_check(out), "vgrid_check")
+        return out[0], out[1], out[2]
+
     def column_path(self):
         """(segment solvers on, column scratch in global memory) as chosen at
         init from N, ROMS_GPU_COLSEG and ROMS_GPU_COL_GLOBAL (roms_gpu_column_path)."""
