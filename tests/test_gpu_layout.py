@@ -10,9 +10,6 @@
   and history files (test_gpu_io.py) and the pipe/river/tide inputs
   (test_gpu_pipes.py, test_gpu_rivers.py, test_gpu_forcing.py) run on the
   padded layout by default.
-* v columns of the momentum segment solvers on 16 x 4 tiles per wavefront
-  (ROMS_GPU_SEG_VTILE, k_colseg.h): the same column arithmetic as rows of 64,
-  so bitwise equal.
 * j-marching per-level horizontal kernels (ROMS_GPU_HJC): windows in an LDS
   ring, same expressions as the 64 x 4 tiles.
 * routines without a data dependence on two streams inside the step
@@ -94,15 +91,6 @@ def test_device_row_pitch_decomposed_bitwise(monkeypatch):
     for r in range(4):
         for f in a[r][4]:
             assert np.array_equal(a[r][4][f], b[r][4][f]), (r, f)
-
-
-def test_seg_vtile_bitwise(monkeypatch):
-    """v columns on 16 x 4 tiles (default) vs rows of 64: pre_step3d and
-    step3d_uv1 segment solvers, C3 switch set at N = 100, bitwise."""
-    a = _run("c3_n100", {"ROMS_GPU_SEG_VTILE": "0"}, monkeypatch, nsteps=3)
-    b = _run("c3_n100", {}, monkeypatch, nsteps=3)
-    for n in FIELDS:
-        assert np.array_equal(a[n], b[n]), n
 
 
 @pytest.mark.parametrize("kind", ["filament_61", "basin_60", "obc_island", "c3_n100"])

@@ -466,26 +466,6 @@ def test_chain_kernels_bitwise_equal_column_sweeps(case, routine, outs, monkeypa
         assert np.array_equal(a[n], b[n]), n
 
 
-@pytest.mark.parametrize("grp", ["1", "2"])
-def test_tile_group_order_bitwise(grp, monkeypatch):
-    """ROMS_GPU_TILE_GRP re-orders the tiles of the hoisted per-level kernels
-    (h_tile: y fastest inside groups of grp x-tiles, a narrower last group);
-    every tile is still computed once: 4 steps equal the plain order bitwise.
-    152 x 40 columns give 3 x-tiles (one full group of 2 and a remainder)."""
-    cfg = basin_cfg(LLm=150, MMm=40, N=8, nonlin=True, sizex=300e3)
-    out = []
-    for env in ("0", grp):
-        monkeypatch.setenv("ROMS_GPU_TILE_GRP", env)
-        m = romsgpu.Model.from_case(cfg.case_id, cfg.LLm, cfg.MMm, cfg.N, cfg.NT, salinity=bool(cfg.salinity),
-                                    nonlin_eos=bool(cfg.nonlin_eos), dt=cfg.dt, ndtfast=cfg.ndtfast,
-                                    sizex=cfg.sizex, sizey=cfg.sizey)
-        m.step(4)
-        out.append({n: m.get(n) for n in ("zeta", "ubar", "vbar", "u", "v", "t", "rufrc", "rvfrc")})
-        m.close()
-    for n in out[0]:
-        assert np.array_equal(out[0][n], out[1][n]), n
-
-
 def test_hz_uv_stored_on_request(monkeypatch):
     """Hz_u/Hz_v (set_depth.F:220,227) feed only extract_data.F; whole steps
     skip their stores unless asked (ROMS_GPU_HZ_UV=1 or a registered host
@@ -536,57 +516,6 @@ def test_step_producer_variants_bitwise(case, switch, monkeypatch):
                                     sizex=cfg.sizex, sizey=cfg.sizey)
         m.step(4)
         out.append({n: m.get(n) for n in ("zeta", "ubar", "vbar", "u", "v", "t", "We", "Wi", "rufrc", "rvfrc")})
-        m.close()
-    for n in out[0]:
-        assert np.array_equal(out[0][n], out[1][n]), n
-
-
-@pytest.mark.parametrize("case", ["filament", "basin"])
-def test_prsgrd_uv_tile_rows_bitwise(case, monkeypatch):
-    """k_prsgrd_uv on 64x8 tiles (ROMS_GPU_PRS_TY=8) equals the 64x4 form
-    bitwise over 4 whole steps (periodic Filament, closed split-EOS basin)."""
-    if case == "basin":
-        cfg = basin_cfg(LLm=70, MMm=42, N=12, nonlin=True)
-    else:
-        cfg = oracle.filament_cfg(LLm=64, MMm=40, N=16, np_xi=1, np_eta=1)
-    out = []
-    for env in ("4", "8"):
-        monkeypatch.setenv("ROMS_GPU_PRS_TY", env)
-        m = romsgpu.Model.from_case(cfg.case_id, cfg.LLm, cfg.MMm, cfg.N, cfg.NT, salinity=bool(cfg.salinity),
-                                    nonlin_eos=bool(cfg.nonlin_eos), dt=cfg.dt, ndtfast=cfg.ndtfast,
-                                    sizex=cfg.sizex, sizey=cfg.sizey)
-        m.step(4)
-        out.append({n: m.get(n) for n in ("zeta", "ubar", "vbar", "u", "v", "t", "rufrc", "rvfrc")})
-        m.close()
-    for n in out[0]:
-        assert np.array_equal(out[0][n], out[1][n]), n
-
-
-@pytest.mark.parametrize("case", ["filament", "basin_odd", "basin_obc_odd"])
-def test_ld16_windows_bitwise(case, monkeypatch):
-    """LDS windows read two doubles per lane (ROMS_GPU_LD16=1, opt-in, needs
-    the padded pitch: k_prsgrd_uv's raw and u/v windows) equal the 8-B form
-    bitwise over 4 whole steps and one prsgrd routine call; odd Lm puts the
-    last pair of a row half outside -1..Lm+2 (its upper double must read as 0)."""
-    if case == "basin_odd":
-        cfg = basin_cfg(LLm=71, MMm=41, N=12, nonlin=True)
-    elif case == "basin_obc_odd":
-        cfg = basin_cfg(LLm=69, MMm=37, N=10, nonlin=True)
-        cfg.obc, cfg.island, cfg.curvgrid = 15, 1, 0
-    else:
-        cfg = oracle.filament_cfg(LLm=64, MMm=40, N=16, np_xi=1, np_eta=1)
-    out = []
-    for env in ("0", "1"):
-        monkeypatch.setenv("ROMS_GPU_LD16", env)
-        m = romsgpu.Model.from_case(cfg.case_id, cfg.LLm, cfg.MMm, cfg.N, cfg.NT, salinity=bool(cfg.salinity),
-                                    nonlin_eos=bool(cfg.nonlin_eos), dt=cfg.dt, ndtfast=cfg.ndtfast,
-                                    sizex=cfg.sizex, sizey=cfg.sizey, obc=cfg.obc, island=bool(cfg.island))
-        m.step(4)
-        r = {n: m.get(n) for n in ("zeta", "ubar", "vbar", "u", "v", "t", "rufrc", "rvfrc")}
-        m.prsgrd()
-        m.sync()
-        r["ru"], r["rv"] = m.get("ru"), m.get("rv")
-        out.append(r)
         m.close()
     for n in out[0]:
         assert np.array_equal(out[0][n], out[1][n]), n

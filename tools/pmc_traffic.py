@@ -26,7 +26,7 @@ ROUTINE_OF = {
     "k_uv2_couple": "step3d_uv2", "k_uv2_flux": "step3d_uv2", "k_step3d_t_h": "step3d_t", "k_step3d_t_v": "step3d_t",
     "k_t3dmix": "t3dmix", "k_step3d_t_seg": "step3d_t", "k_periodic_wrap": "halo", "k_halo_pack": "halo", "k_halo_unpack": "halo",
     # round-2 kernels: register / segment / chained forms
-    "k_uv1_reg": "step3d_uv1", "k_uv1_seg": "step3d_uv1", "k_pre_tracer_v_reg": "pre_step3d",
+    "k_uv1_seg": "step3d_uv1", "k_pre_tracer_v_reg": "pre_step3d",
     "k_pre_tracer_seg": "pre_step3d", "k_pre_uv_seg": "pre_step3d", "k_uv2_fused": "step3d_uv2",
     "k_set_huv1_chain": "set_HUV1", "k_kpp_ext": "lmd_vmix", "k_kpp_int": "lmd_vmix", "k_prsgrd_fused": "prsgrd",
     "k_bulk_flux": "bulk_flux", "k_t3dbc_edges": "step3d_t", "k_t3dbc_corners": "step3d_t", "k_u3dbc": "step3d_uv2",

@@ -359,15 +359,13 @@ __device__ __forceinline__ void uv_spline_seg(const Dev& d, const SegSpan& sg, S
 
 // uv_spline_seg with buffer loads (the segment solvers' buffer forms): the
 // lane's column and its (i-1)/(j-1), (i+1)/(j+1), (i-2)/(j-2) neighbours in
-// four VGPR offsets, each row's level in an SGPR (seg_uniform).  row(q, so,
-// h0, h1, u) gets the row's level byte offset in place of the element offset.
+// four VGPR offsets, each row's level added to them.  row(q, so, h0, h1, u)
+// gets the row's level byte offset in place of the element offset.
 // Same expressions and order: bitwise equal to uv_spline_seg.
 struct NoSplineRowB {
   __device__ __forceinline__ void operator()(int, unsigned, double, double, double) const {}
 };
-// UNI: the segment is wave-uniform (seg_uniform) and level offsets go in
-// the SGPR soffset; else they are added to the VGPR offset.
-template <int KR, bool UNI = true, class RowF = NoSplineRowB>
+template <int KR, class RowF = NoSplineRowB>
 __device__ __forceinline__ void uv_spline_segb(const Dev& d, const SegSpan& sg, SegXchg& X, long ij, int nrhs, int dir,
                                                double (&fl)[KR], RowF row = RowF()) {
   const Bounds& b = d.b;
@@ -383,7 +381,7 @@ __device__ __forceinline__ void uv_spline_segb(const Dev& d, const SegSpan& sg, 
   const unsigned vm = vo - ds, vp = vo + ds, vm2 = vo - 2u * ds;
   const BufF64 Uv((dir == 0 ? F.u : F.v) + (long)(nrhs - 1) * b.n3), Hz(F.Hz), We(F.We);
   const double* mask = dir == 0 ? F.umask : F.vmask;
-  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return UNI ? B.ld(v, l) : B.ld(v + l, 0u); };
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
   double dc[KR + 1], uu[KR];
 #pragma unroll
   for (int q = 0; q < KR + 1; q++) {
@@ -437,43 +435,19 @@ __device__ __forceinline__ void tracer_spline_seg(const SegSpan& sg, int N, long
 // i >= istrU, 1: v at j >= jstrV), kSegCW columns x blockDim.z rows j per block.
 // Lanes outside the column range (i or j) solve a clamped duplicate column
 // (they take part in the barriers) and store nothing.
-// v columns (Params::seg_vtile, kSegCW = 64): a wavefront's 64 lanes hold a
-// 16 x 4 tile of columns instead of one row of 64.  The v stencils read the
-// rows j-2..j+1 of Hz and We and j-1 of Hz_fwd/bak, Akv, Wi; with one row per
-// wavefront every one of those rows is another block's row and comes from
-// HBM again (no L2 reuse at ~1 MB of columns per block), with four rows per
-// wavefront the tile's 7 (4) distinct rows serve its 16 (8) row reads.  A
-// 16-wide row is one 128-B line at the device row pitch (roms_dev.h).  The
-// blocks of the two directions enumerate their own tiles; a block whose
-// tile lies outside the range is idle (returns before any barrier).
-// (16 x 4 at 64 columns; the 8 x 4 tiles of 32-column segments measured
-// much slower, C3 58.3 vs 53.9 ms, r5_r_vtile_cw32_ab.txt, so segments of 32
-// columns keep their v columns in rows)
-constexpr int kVTX = 16, kVTY = 4;
 struct SegCol {
   int i, j, dir;
   bool act, idle;
 };
-__device__ __forceinline__ bool seg_vtile_on(const Dev& d) { return d.p.seg_vtile && kSegCW == kVTX * kVTY; }
 __device__ __forceinline__ void seg_uv_col(const Dev& d, const Range& R, const uint3& bI, const SegSpan& sg,
                                            SegCol& c) {
   const Bounds& b = d.b;
   c.dir = (int)bI.z;
   const int ilo = c.dir == 0 ? b.istrU : b.istr;
   const int jlo = c.dir == 1 ? (b.jstrV > R.j0 ? b.jstrV : R.j0) : R.j0;
-  int iu, ju;
-  if (c.dir == 1 && seg_vtile_on(d)) {
-    const int ti0 = tile_i0(R.i0);
-    const int ntx = (R.i1 - ti0 + kVTX) / kVTX, nty = (R.j1 - R.j0 + kVTY) / kVTY;
-    const int t = (int)bI.x + (int)gridDim.x * (int)bI.y;
-    c.idle = t >= ntx * nty;
-    iu = ti0 + (t % ntx) * kVTX + sg.col % kVTX;
-    ju = R.j0 + (t / ntx) * kVTY + sg.col / kVTX;
-  } else {
-    iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
-    ju = R.j0 + (int)bI.y * (int)blockDim.z + sg.row;
-    c.idle = R.j0 + (int)bI.y * (int)blockDim.z > R.j1;
-  }
+  const int iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
+  const int ju = R.j0 + (int)bI.y * (int)blockDim.z + sg.row;
+  c.idle = R.j0 + (int)bI.y * (int)blockDim.z > R.j1;
   c.act = iu >= ilo && iu <= R.i1 && ju >= jlo && ju <= R.j1;
   c.i = iu < ilo ? ilo : (iu > R.i1 ? R.i1 : iu);
   c.j = ju < jlo ? jlo : (ju > R.j1 ? R.j1 : ju);
@@ -481,16 +455,7 @@ __device__ __forceinline__ void seg_uv_col(const Dev& d, const Range& R, const u
 inline dim3 seg_grid_of(const Range& R, int nz, int jrows = 1) {
   return dim3((R.i1 - tile_i0(R.i0) + kSegCW) / kSegCW, (R.j1 - R.j0 + jrows) / jrows, nz);
 }
-// the momentum kernels' grid: enough blocks in (x, y) for the u rows and for
-// the v tiles (seg_uv_col)
-inline dim3 seg_uv_grid(const Dev& d, const Range& R, int jrows) {
-  dim3 g = seg_grid_of(R, 2, jrows);
-  if (d.p.seg_vtile && kSegCW == kVTX * kVTY && jrows == 1) {
-    const long nvt = (long)((R.i1 - tile_i0(R.i0) + kVTX) / kVTX) * ((R.j1 - R.j0 + kVTY) / kVTY);
-    const long gy = (nvt + g.x - 1) / g.x;
-    if (gy > (long)g.y) g.y = (unsigned)gy;
-  }
-  return g;
-}
+// the momentum kernels' grid (seg_uv_col): grid z = direction
+inline dim3 seg_uv_grid(const Dev& d, const Range& R, int jrows) { return seg_grid_of(R, 2, jrows); }
 
 }  // namespace roms

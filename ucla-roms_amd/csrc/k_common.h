@@ -174,7 +174,7 @@ __device__ __forceinline__ void tracer_spline_lds(int N, long n2, const double* 
 }
 
 // ---- register-resident form of tracer_spline_lds for a compile-time depth
-// NN (the k_uv1_reg pattern): FC lives in A[0..NN] (VGPRs), CF in one LDS
+// NN: FC lives in A[0..NN] (VGPRs), CF in one LDS
 // slot B, and every level loop is fully unrolled so each A[k] is a fixed
 // register and the compiler schedules the (alias-free) global loads ahead.
 // Same expressions and order as tracer_spline_lds: bit-identical results. ----
@@ -327,13 +327,6 @@ inline dim3 grid3_jc(const Range& r, int nk, int jc) {
   if (ni < 1) ni = 1;
   if (nj < 1) nj = 1;
   return dim3((ni + kBX - 1) / kBX, (nj + jc - 1) / jc, nk);
-}
-// grid of the per-level horizontal kernels with 64 x ty tiles (Params::h_ty)
-inline dim3 grid3_ty(const Range& r, int nk, int ty) {
-  int ni = r.i1 - tile_i0(r.i0) + 1, nj = r.j1 - r.j0 + 1;
-  if (ni < 1) ni = 1;
-  if (nj < 1) nj = 1;
-  return dim3((ni + kBX - 1) / kBX, (nj + ty - 1) / ty, nk);
 }
 
 // ---- horizontal momentum r.h.s. (Coriolis + advection) at (i,j,k) ----
@@ -646,58 +639,6 @@ __device__ __forceinline__ void uv_vert_flux_lds(const Dev& d, long ij, int nrhs
   A[0] = 0.0;
   A[N] = 0.0;
 }
-// ---- SPLINE_UV flux of a u (dir 0) / v (dir 1) column for a compile-time
-// depth NN: FC in registers A[0..NN], CF in one LDS slot B; on exit A[k] is
-// the vertical advective flux at w-level k (A[0] = A[N] = 0), exactly as
-// uv_vert_flux_lds leaves it.  Used by k_uv1_reg and k_pre_uv_reg. ----
-template <int NN>
-__device__ __forceinline__ void uv_spline_reg(const Dev& d, long ij, int nrhs, int dir, double (&A)[NN + 1],
-                                              const ColLds& B) {
-  const Bounds& b = d.b;
-  const Fields& F = d.f;
-  constexpr int N = NN;
-  const long n2 = b.n2;
-  const long s = dir == 0 ? 1 : b.nx2;
-  if (!d.p.uv_adv) {
-#pragma unroll
-    for (int k = 0; k <= N; k++) A[k] = 0.0;
-  } else {
-    const double* __restrict__ Uv = (dir == 0 ? F.u : F.v) + (long)(nrhs - 1) * b.n3 + ij;
-    const double* __restrict__ Hz = F.Hz + ij;
-    const double* __restrict__ We = F.We + ij;
-    const double* mask = dir == 0 ? F.umask : F.vmask;
-    auto DCk = [&](int k) {
-      const long o = (long)(k - 1) * n2;
-      return 0.5625 * (Hz[o] + Hz[o - s]) - 0.0625 * (Hz[o + s] + Hz[o - 2 * s]);
-    };
-    double dck = DCk(1), cfk = 1.0, fcm = 2.0 * Uv[0], uk = Uv[0];
-#pragma unroll
-    for (int k = 1; k <= N - 1; k++) {
-      const double dc1 = DCk(k + 1), uk1 = Uv[(long)k * n2];
-      const double cff = 1.0 / (2.0 * dck + dc1 * (2.0 - cfk));
-      const double cf1 = cff * dck;
-      const double fck = cff * (3.0 * (dck * uk1 + dc1 * uk) - dc1 * fcm);
-      B[k + 1] = cf1;
-      A[k] = fck;
-      dck = dc1; cfk = cf1; fcm = fck; uk = uk1;
-      ROMS_LEVEL_FENCE_AT(k);
-    }
-    double fc1 = (2.0 * Uv[(long)(N - 1) * n2] - fcm) / (1.0 - cfk);  // FC(N)
-    const double m1 = mask[ij + s], m0 = mask[ij - s];
-#pragma unroll
-    for (int k = N - 1; k >= 1; k--) {
-      const long w = (long)k * n2;
-      const double wf = We[w] + We[w - s] - 0.125 * ((We[w + s] - We[w]) * m1 - (We[w - s] - We[w - 2 * s]) * m0);
-      const double fck = A[k] - B[k + 1] * fc1;
-      A[k] = fck * 0.5 * wf;
-      fc1 = fck;
-      ROMS_LEVEL_FENCE_AT(k);
-    }
-    A[0] = 0.0;
-    A[N] = 0.0;
-  }
-}
-
 template <class C>
 __device__ __forceinline__ double uv_rr_update(double r, const C& A, int k) {
   return k == 1 ? r - A[1] : r - A[k] + A[k - 1];

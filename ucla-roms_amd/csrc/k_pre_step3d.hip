@@ -64,31 +64,31 @@ __global__ void __launch_bounds__(256) k_pre_tracer_h(Dev d, Range R, PreCoef c,
 // for memory once instead of once per phase.  The per-phase form above waits
 // 2 + 2 NT times and, with ~7 blocks per CU, was bound by those round trips,
 // not by bandwidth.  Same expressions in the same order: bit-identical. ----
-template <int NTT, int TY>
+template <int NTT>
 struct TracerWinN {
-  static constexpr int kN = kUVW * (TY + 4);
+  static constexpr int kN = kUVW * (kBY + 4);
   double UM[kN], VM[kN], FU[kN], FV[kN], T[NTT][kN];
 };
 // kHB: the interior cells' Hz_bak / Hz_fwd are already in c3 / c2 (the
 // predictor's k_omega_seg<true> formed them with this expression); those
 // cells load Hz_bak instead of the fluxes and We/Wi, the ring i = istr-1 /
 // j = jstr-1 still forms both.
-template <int NTT, int TY, bool kHB>
-__global__ void __launch_bounds__(kBX * TY) k_pre_tracer_h1(Dev d, Range R, PreCoef c, int nstp, int nnew, int nrhs) {
-  const uint3 bI = h_tile(d.p.tile_grp);
-  __shared__ TracerWinN<NTT, TY> W;
+template <int NTT, bool kHB>
+__global__ void __launch_bounds__(kBX * kBY) k_pre_tracer_h1(Dev d, Range R, PreCoef c, int nstp, int nnew, int nrhs) {
+  const uint3 bI = xcd_tile();
+  __shared__ TracerWinN<NTT> W;
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int k = 1 + (int)bI.z, indx = 3 - nstp;
-  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * TY;
+  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * kBY;
   const int ib = i0 - 2, jb = j0 - 2;
   const long kk = (long)(k - 1) * b.n2, n2 = b.n2;
   const int tid = threadIdx.x + kBX * threadIdx.y;
-  constexpr int NW = kUVW * (TY + 4), NR = (NW + kBX * TY - 1) / (kBX * TY);
+  constexpr int NW = kUVW * (kBY + 4), NR = (NW + kBX * kBY - 1) / (kBX * kBY);
   double wUM[NR], wVM[NR], wFU[NR], wFV[NR], wT[NTT][NR];
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     const int i = ib + q % kUVW, j = jb + q / kUVW;
     const bool ok = q < NW && i >= -1 && i <= b.Lm + 2 && j >= -1 && j <= b.Mm + 2;
     const long o = ok ? IJ(b, i, j) : 0;
@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(kBX * TY) k_pre_tracer_h1(Dev d, Range R, PreC
   }
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     if (q < NW) {
       W.UM[q] = wUM[r]; W.VM[q] = wVM[r]; W.FU[q] = wFU[r]; W.FV[q] = wFV[r];
 #pragma unroll
@@ -485,15 +485,14 @@ __global__ void __launch_bounds__(256) k_uv_horiz(Dev d, Range R, int nrhs, UVBo
 // The same without CURVGRID with every global load issued at block entry
 // (the window and the lane's own ru, rv, Hz, fomn): one memory wait per
 // block.  Bit-identical.
-template <int TY>
-__global__ void __launch_bounds__(kBX * TY) k_uv_horiz1(Dev d, Range R, int nrhs, UVBounds ub, int up) {
-  const uint3 bI = h_tile(d.p.tile_grp);
-  constexpr int NW = kUVW * (TY + 4);
+__global__ void __launch_bounds__(kBX * kBY) k_uv_horiz1(Dev d, Range R, int nrhs, UVBounds ub, int up) {
+  const uint3 bI = xcd_tile();
+  constexpr int NW = kUVW * (kBY + 4);
   __shared__ double sU[NW], sV[NW], sFU[NW], sFV[NW];
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int k = 1 + (int)bI.z;
-  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * TY;
+  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * kBY;
   const int ib = i0 - 2, jb = j0 - 2;
   const long kk = (long)(k - 1) * b.n2;
   const double* U = F.u + (long)(nrhs - 1) * b.n3 + kk;
@@ -503,11 +502,11 @@ __global__ void __launch_bounds__(kBX * TY) k_uv_horiz1(Dev d, Range R, int nrhs
   const int i = i0 + (int)threadIdx.x, j = j0 + (int)threadIdx.y;
   const bool act = i >= R.i0 && i <= R.i1 && j <= R.j1;
   const int tid = threadIdx.x + kBX * threadIdx.y;
-  constexpr int NR = (NW + kBX * TY - 1) / (kBX * TY);
+  constexpr int NR = (NW + kBX * kBY - 1) / (kBX * kBY);
   double wU[NR], wV[NR], wFU[NR], wFV[NR];
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     const int ii = ib + q % kUVW, jj = jb + q / kUVW;
     const bool ok = q < NW && ii >= -1 && ii <= b.Lm + 2 && jj >= -1 && jj <= b.Mm + 2;
     const long o = ok ? IJ(b, ii, jj) : 0;
@@ -526,7 +525,7 @@ __global__ void __launch_bounds__(kBX * TY) k_uv_horiz1(Dev d, Range R, int nrhs
   }
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     if (q < NW) { sU[q] = wU[r]; sV[q] = wV[r]; sFU[q] = wFU[r]; sFV[q] = wFV[r]; }
   }
   __syncthreads();
@@ -543,10 +542,8 @@ void launch_uv_horiz(const Dev& d, hipStream_t s, int nrhs, int up) {
   const UVBounds ub = uv_bounds(b);
   if (!d.p.hoist || d.p.curvgrid)
     hipLaunchKernelGGL(k_uv_horiz, grid3_of(R, b.N), dim3(kBX, kBY), 0, s, d, R, nrhs, ub, up);
-  else if (d.p.h_ty == 8)
-    hipLaunchKernelGGL(k_uv_horiz1<8>, grid3_ty(R, b.N, 8), dim3(kBX, 8), 0, s, d, R, nrhs, ub, up);
   else
-    hipLaunchKernelGGL(k_uv_horiz1<4>, grid3_ty(R, b.N, 4), dim3(kBX, 4), 0, s, d, R, nrhs, ub, up);
+    hipLaunchKernelGGL(k_uv_horiz1, grid3_of(R, b.N), dim3(kBX, kBY), 0, s, d, R, nrhs, ub, up);
 }
 
 // ---- bottom drag r_D (compute_rd_bott_drag.h), log-layer with Zob ----
@@ -766,11 +763,8 @@ __global__ void __launch_bounds__(kSegBlock, 2) k_pre_tracer_seg(Dev d, Range R,
 }
 
 // ---- k_pre_tracer_seg with buffer loads/stores (Params::seg_buf, see
-// k_step3d_t_segb): wave-uniform level offsets in SGPRs, the lane's column in
-// one VGPR.  PF: the diffusion phase's t(nnew) rows and Hz_fwd loaded at
-// entry with the spline inputs.  Same expressions and order: bitwise equal
-// to k_pre_tracer_seg. ----
-template <bool PF, bool UNI = true>
+// k_step3d_t_segb): the lane's column and the level offset in one VGPR
+// offset.  Same expressions and order: bitwise equal to k_pre_tracer_seg. ----
 __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_segb(Dev d, Range R, PreCoef c, int nnew,
                                                                                    int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
@@ -779,15 +773,8 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int N = b.N;
-  SegSpan sg = seg_span(N);
-  constexpr bool kU = UNI && kSegCW == kCX;   // scalar level offsets need one segment per wavefront
-  if constexpr (kU) seg_uniform(sg);
-  // UNI: level offsets in the SGPR soffset; else added to the VGPR offset
-  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return kU ? B.ld(v, l) : B.ld(v + l, 0u); };
-  auto ST = [&](const BufF64& B, double x, unsigned v, unsigned l) {
-    if constexpr (kU) B.st(x, v, l);
-    else B.st(x, v + l, 0u);   // v = kBufOff stays beyond the extent
-  };
+  const SegSpan sg = seg_span(N);
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
   const int iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
   const bool act = iu >= R.i0 && iu <= R.i1;
   const int i = act ? iu : (iu < R.i0 ? R.i0 : R.i1), j = R.j0 + (int)bI.y;
@@ -800,18 +787,11 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
   const BufF64 Hz(F.Hz), Hf(F.c2), We(F.We), Wi(F.Wi);
   const long tb = (long)(itrc - 1) * 3 * b.n3;
   const BufF64 Tr(F.t + (long)(nrhs - 1) * b.n3 + tb), Tn(F.t + (long)(nnew - 1) * b.n3 + tb);
-  double hz[KR + 1], tt[KR], fl[KR], hf[KR + 1], tn[KR];
+  double hz[KR + 1], tt[KR], fl[KR];
 #pragma unroll
   for (int q = 0; q < KR + 1; q++) {
     hz[q] = LD(Hz, vo, lev(c0 - 1 + q));
     if (q < KR) tt[q] = LD(Tr, vo, lev(c0 - 1 + q));
-  }
-  if constexpr (PF) {
-#pragma unroll
-    for (int q = 0; q < KR + 1; q++) {
-      hf[q] = LD(Hf, vo, lev(c0 - 1 + q));
-      if (q < KR) tn[q] = LD(Tn, vo, lev(c0 + q));
-    }
   }
   spline_fc_seg<KR>(sg, N, X, hz, tt, fl);
   {
@@ -828,7 +808,7 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int q = 0; q < KR + 1; q++) hz[q] = PF ? hf[q] : LD(Hf, vo, lev(c0 - 1 + q));
+  for (int q = 0; q < KR + 1; q++) hz[q] = LD(Hf, vo, lev(c0 - 1 + q));
   const int iAkt = itrc < b.nTS ? itrc : b.nTS;
   const BufF64 Akt(F.Akt + (long)(iAkt - 1) * b.n3w);
   const BufF64 Pm(F.pm), Pn(F.pn);   // 2-D metrics through the lane's offset too (no 64-bit ij kept live)
@@ -854,7 +834,7 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
     a = -(fcl + fmax0(wcl));
     bb = hz[p + 1] + fcu + fmax0(wcu) + fcl - fmin0(wcl);
     cc = -(fcu - fmin0(wcu));
-    dd = (PF ? tn[p] : LD(Tn, vo, lev(c0 + p))) - c.dtau * pm * pn * (fl[p + 1 < KR ? p + 1 : KR - 1] - fl[p]);
+    dd = LD(Tn, vo, lev(c0 + p)) - c.dtau * pm * pn * (fl[p + 1 < KR ? p + 1 : KR - 1] - fl[p]);
     fcl = fcu; wcl = wcu;
   });
   double xL, xR;
@@ -863,7 +843,7 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
   const unsigned vs = act ? vo : kBufOff;
 #pragma unroll
   for (int p = 0; p < KR; p++)
-    if (p < n) ST(Tn, T.D[p], vs, lev(c0 + p));
+    if (p < n) Tn.st(T.D[p], vs + lev(c0 + p), 0u);   // vs = kBufOff stays beyond the extent
 }
 
 // kLds (UV_ADV, nrhs == nstp -- always so in the predictor): the spline
@@ -989,12 +969,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_seg(Dev d, R
   }
 }
 
-// ---- k_pre_uv_seg<true> with buffer loads/stores (Params::seg_buf bit
-// 128): wave-uniform level offsets in SGPRs (seg_uniform), the lane's column
-// and its neighbour in VGPR offsets.  Same expressions and order: bitwise
-// equal to k_pre_uv_seg<true>.  PF: the viscosity rows' Hz_fwd pairs
-// loaded at entry with the spline inputs. ----
-template <bool PF, bool UNI = true>
+// ---- k_pre_uv_seg<true> with buffer loads/stores (Params::seg_buf): the
+// lane's column and its neighbour, plus the level offset, in VGPR offsets.
+// Same expressions and order: bitwise equal to k_pre_uv_seg<true>. ----
 __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, Range R, PreCoef c, int nstp, int nnew,
                                                                          int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
@@ -1003,15 +980,8 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int N = b.N, indx = 3 - nstp;
-  SegSpan sg = seg_span(N);
-  constexpr bool kU = UNI && kSegCW == kCX;   // scalar level offsets need one segment per wavefront
-  if constexpr (kU) seg_uniform(sg);
-  // UNI: level offsets in the SGPR soffset; else added to the VGPR offset
-  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return kU ? B.ld(v, l) : B.ld(v + l, 0u); };
-  auto ST = [&](const BufF64& B, double x, unsigned v, unsigned l) {
-    if constexpr (kU) B.st(x, v, l);
-    else B.st(x, v + l, 0u);   // v = kBufOff stays beyond the extent
-  };
+  const SegSpan sg = seg_span(N);
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
   SegCol col;
   seg_uv_col(d, R, bI, sg, col);
   if (col.idle) return;   // uniform over the block
@@ -1028,17 +998,8 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
   double* const Su = roms_smem + (long)(KR - 1) * nthr + tid;  // row q-1: Hz*u(nstp), the new u(indx)
   const BufF64 Uix(Uall + (long)(indx - 1) * b.n3), Unew(Uall + (long)(nnew - 1) * b.n3), Hf(F.c2);
   double hf[KR + 1], hfm[KR + 1];   // Hz_fwd(c0-1+q) of the column and of its (i-1) / (j-1) neighbour
-  auto load_hf = [&] {
-#pragma unroll
-    for (int q = 0; q < KR + 1; q++) {
-      const unsigned L = lev(c0 - 1 + q);
-      hf[q] = LD(Hf, vo, L);
-      hfm[q] = LD(Hf, vm, L);
-    }
-  };
-  if constexpr (PF) load_hf();
   double fl[KR];
-  uv_spline_segb<KR, kU>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned L, double h0, double h1, double u) {
+  uv_spline_segb<KR>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned L, double h0, double h1, double u) {
     if (q >= 1 && q < KR) {   // cells c0..c0+KR-2 (q is a constant of the unrolled load loop)
       Sb[(q - 1) * nthr] = c.cf_stp * u + c.cf_bak * LD(Uix, vo, L);
       Su[(q - 1) * nthr] = 0.5 * (h0 + h1) * u;
@@ -1057,7 +1018,12 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
     const double v = 0.5 * (LD(Hb, vo, o) + LD(Hb, vm, o)) * ub + DC0 * r;
     return k == N ? v + c.dtau * sstr : v;
   };
-  if constexpr (!PF) load_hf();
+#pragma unroll
+  for (int q = 0; q < KR + 1; q++) {
+    const unsigned L = lev(c0 - 1 + q);
+    hf[q] = LD(Hf, vo, L);
+    hfm[q] = LD(Hf, vm, L);
+  }
   auto fcw = [&](int q, double& fc, double& wc) {   // interface c0-1+q (0 at the bottom and the surface)
     const int r = c0 - 1 + q;
     const unsigned w = (unsigned)min(max(r, 1), N - 1) * lv;
@@ -1093,8 +1059,8 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
   for (int p = 0; p < KR; p++)
     if (p < n) {
       const unsigned o = lev(c0 + p);
-      ST(Unew, T.D[p], vs, o);
-      ST(Uix, Su[(p < KR - 1 ? p : KR - 2) * nthr], vs, o);
+      Unew.st(T.D[p], vs + o, 0u);   // vs = kBufOff stays beyond the extent
+      Uix.st(Su[(p < KR - 1 ? p : KR - 2) * nthr], vs + o, 0u);
     }
 }
 
@@ -1104,13 +1070,7 @@ static size_t pre_uv_seg_lds_bytes(unsigned nthr) {
 void setup_pre_uv_seg() {
   (void)hipFuncSetAttribute((const void*)k_pre_uv_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
 }
 
@@ -1148,93 +1108,63 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   // horizontal part on rows rh (the ring i = istr-1, j = jstr-1 included):
   // the rows strips cover (k_tracer_strip.hip), the rest on tiles
   auto horiz_tiles = [&](const Range& rh) {
+    const dim3 gh = grid3_of(rh, b.N), bh(kBX, kBY);
     if (d.p.hoist && d.p.h_jc > 0 && (b.NT == 1 || b.NT == 2)) {
-      const dim3 g = grid3_jc(rh, b.N, d.p.h_jc), bs(kBX, kBY);
+      const dim3 g = grid3_jc(rh, b.N, d.p.h_jc);
       const int jc = d.p.h_jc;
       if (b.NT == 2 && hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_hj<2, true>), g, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
+        hipLaunchKernelGGL((k_pre_tracer_hj<2, true>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
       else if (b.NT == 2)
-        hipLaunchKernelGGL((k_pre_tracer_hj<2, false>), g, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
+        hipLaunchKernelGGL((k_pre_tracer_hj<2, false>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
       else if (hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_hj<1, true>), g, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
+        hipLaunchKernelGGL((k_pre_tracer_hj<1, true>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
       else
-        hipLaunchKernelGGL((k_pre_tracer_hj<1, false>), g, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
-    } else if (d.p.hoist && b.NT == 2 && d.p.h_ty == 8) {
-      if (hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_h1<2, 8, true>), grid3_ty(rh, b.N, 8), dim3(kBX, 8), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-      else
-        hipLaunchKernelGGL((k_pre_tracer_h1<2, 8, false>), grid3_ty(rh, b.N, 8), dim3(kBX, 8), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-    } else if (d.p.hoist && b.NT == 2) {
-      if (hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_h1<2, 4, true>), grid3_ty(rh, b.N, 4), dim3(kBX, 4), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-      else
-        hipLaunchKernelGGL((k_pre_tracer_h1<2, 4, false>), grid3_ty(rh, b.N, 4), dim3(kBX, 4), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-    } else if (d.p.hoist && b.NT == 1) {
-      if (hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_h1<1, 4, true>), grid3_ty(rh, b.N, 4), dim3(kBX, 4), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-      else
-        hipLaunchKernelGGL((k_pre_tracer_h1<1, 4, false>), grid3_ty(rh, b.N, 4), dim3(kBX, 4), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-    } else {
-      hipLaunchKernelGGL(k_pre_tracer_h, grid3_of(rh, b.N), dim3(kBX, kBY), 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
-    }
+        hipLaunchKernelGGL((k_pre_tracer_hj<1, false>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
+    } else if (d.p.hoist && b.NT == 2 && hb_done)
+      hipLaunchKernelGGL((k_pre_tracer_h1<2, true>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+    else if (d.p.hoist && b.NT == 2)
+      hipLaunchKernelGGL((k_pre_tracer_h1<2, false>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+    else if (d.p.hoist && b.NT == 1 && hb_done)
+      hipLaunchKernelGGL((k_pre_tracer_h1<1, true>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+    else if (d.p.hoist && b.NT == 1)
+      hipLaunchKernelGGL((k_pre_tracer_h1<1, false>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+    else
+      hipLaunchKernelGGL(k_pre_tracer_h, gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
   };
-  auto horiz = [&](const Range& rh) {
+  {
     int jA = 0, jB = -1;
     if (d.p.hoist && d.p.h_jc == 0 &&
-        launch_tracer_strip(d, s, rh, 1, false, hb_done, t.nnew, t.nrhs, c.dtau, c.cf_stp, c.cf_bak, t.nstp, jA, jB)) {
-      if (jA > rh.j0) horiz_tiles(Range{rh.i0, rh.i1, rh.j0, jA - 1});
-      if (jB < rh.j1) horiz_tiles(Range{rh.i0, rh.i1, jB + 1, rh.j1});
+        launch_tracer_strip(d, s, RH, 1, false, hb_done, t.nnew, t.nrhs, c.dtau, c.cf_stp, c.cf_bak, t.nstp, jA, jB)) {
+      if (jA > RH.j0) horiz_tiles(Range{RH.i0, RH.i1, RH.j0, jA - 1});
+      if (jB < RH.j1) horiz_tiles(Range{RH.i0, RH.i1, jB + 1, RH.j1});
     } else {
-      horiz_tiles(rh);
+      horiz_tiles(RH);
     }
-  };
-  // column solves on rows ri
-  auto cols = [&](const Range& ri, hipStream_t st) {
-    dim3 gt = gridc_of(ri);
-    gt.z = b.NT;
-    if (d.p.colseg && (d.p.seg_buf & 1) && (d.p.seg_buf & 16))
-      hipLaunchKernelGGL(k_pre_tracer_segb<true>, seg_grid_of(ri, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, ri, c,
-                         t.nnew, t.nrhs);
-    else if (d.p.colseg && (d.p.seg_buf & 1) && (d.p.seg_buf & 1024))
-      hipLaunchKernelGGL((k_pre_tracer_segb<false, false>), seg_grid_of(ri, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, ri,
-                         c, t.nnew, t.nrhs);
-    else if (d.p.colseg && (d.p.seg_buf & 1))
-      hipLaunchKernelGGL(k_pre_tracer_segb<false>, seg_grid_of(ri, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, ri, c,
-                         t.nnew, t.nrhs);
-    else if (d.p.colseg)
-      hipLaunchKernelGGL(k_pre_tracer_seg, seg_grid_of(ri, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, ri, c, t.nnew,
-                         t.nrhs);
-    else if ((d.p.colreg & 2) && b.N == 50 && !d.f.colscr)
-      hipLaunchKernelGGL(k_pre_tracer_v_reg<50>, gt, dim3(kCX), col_lds_bytes(1, 50), st, d, ri, c, t.nnew, t.nrhs);
-    else if (d.f.colscr)
-      hipLaunchKernelGGL(k_pre_tracer_v<ColGlb>, gt, dim3(kCX), 0, st, d, ri, c, t.nnew, t.nrhs);
-    else
-      hipLaunchKernelGGL(k_pre_tracer_v<ColLds>, gt, dim3(kCX), col_lds_bytes(2, b.N), st, d, ri, c, t.nnew, t.nrhs);
-  };
-  // Params::t_chunk: horizontal part and column solves alternate over strips
-  // of t_chunk rows, so each strip's t(nnew) -- the horizontal result the
-  // solver reads back -- is still in the Infinity Cache when it is read
-  if (d.p.t_chunk > 0 && !side && d.p.colseg) {
-    for (int ja = b.jstr; ja <= b.jend; ja += d.p.t_chunk) {
-      const int jb = min(ja + d.p.t_chunk - 1, b.jend);
-      horiz(Range{b.istr - 1, b.iend, ja == b.jstr ? b.jstr - 1 : ja, jb});
-      cols(Range{b.istr, b.iend, ja, jb}, s);
-    }
-  } else {
-    horiz(RH);
-    // The tracer column solves (t(nnew), reading Hz_fwd) and the momentum ones
-    // (u, v(nnew), u, v(indx), reading Hz_fwd/bak, ru, rv) share no output:
-    // with a side stream they run side by side once the horizontal tracer
-    // kernel has formed the ring of Hz_fwd/bak both read
-    hipStream_t st = s;
-    if (side) {
-      (void)hipEventRecord(side->efork, s);
-      (void)hipStreamWaitEvent(side->s2, side->efork, 0);
-      st = side->s2;
-    }
-    cols(RI, st);
   }
-  hipStream_t st = side ? side->s2 : s;
+  // The tracer column solves (t(nnew), reading Hz_fwd) and the momentum ones
+  // (u, v(nnew), u, v(indx), reading Hz_fwd/bak, ru, rv) share no output:
+  // with a side stream they run side by side once the horizontal tracer
+  // kernel has formed the ring of Hz_fwd/bak both read
+  hipStream_t st = s;
+  if (side) {
+    (void)hipEventRecord(side->efork, s);
+    (void)hipStreamWaitEvent(side->s2, side->efork, 0);
+    st = side->s2;
+  }
+  dim3 gt = gridc_of(RI);
+  gt.z = b.NT;
+  if (d.p.colseg && d.p.seg_buf)
+    hipLaunchKernelGGL(k_pre_tracer_segb, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, RI, c, t.nnew,
+                       t.nrhs);
+  else if (d.p.colseg)
+    hipLaunchKernelGGL(k_pre_tracer_seg, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, RI, c, t.nnew,
+                       t.nrhs);
+  else if ((d.p.colreg & 2) && b.N == 50 && !d.f.colscr)
+    hipLaunchKernelGGL(k_pre_tracer_v_reg<50>, gt, dim3(kCX), col_lds_bytes(1, 50), st, d, RI, c, t.nnew, t.nrhs);
+  else if (d.f.colscr)
+    hipLaunchKernelGGL(k_pre_tracer_v<ColGlb>, gt, dim3(kCX), 0, st, d, RI, c, t.nnew, t.nrhs);
+  else
+    hipLaunchKernelGGL(k_pre_tracer_v<ColLds>, gt, dim3(kCX), col_lds_bytes(2, b.N), st, d, RI, c, t.nnew, t.nrhs);
   for (int itrc = 1; itrc <= b.NT && side; itrc++) launch_t3dbc(d, st, t, itrc);
   if (side) launch_exchange_tracers(d, st, t.nnew);
   if (!uv_done) launch_uv_horiz(d, s, t.nrhs, 0);
@@ -1244,22 +1174,12 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   gu.z = 2;
   if (d.p.colseg) {
     const dim3 gs = seg_uv_grid(d, RI, d.p.seg_jrows), bs(kCX, seg_waves(b.N), d.p.seg_jrows);
+    const bool lds = d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp;
     ktimer_mark(s, kTimedPreUvSeg, 0);
-    if (d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp && (d.p.seg_buf & 128) && (d.p.seg_buf & 256) &&
-        !(d.p.seg_buf & 512))
-      hipLaunchKernelGGL(k_pre_uv_segb<true>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp,
-                         t.nnew, t.nrhs);
-    else if (d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp && (d.p.seg_buf & 128) && (d.p.seg_buf & 512) &&
-             (d.p.seg_buf & 256))
-      hipLaunchKernelGGL((k_pre_uv_segb<true, false>), gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c,
-                         t.nstp, t.nnew, t.nrhs);
-    else if (d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp && (d.p.seg_buf & 128) && (d.p.seg_buf & 512))
-      hipLaunchKernelGGL((k_pre_uv_segb<false, false>), gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c,
-                         t.nstp, t.nnew, t.nrhs);
-    else if (d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp && (d.p.seg_buf & 128))
-      hipLaunchKernelGGL(k_pre_uv_segb<false>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp, t.nnew,
+    if (lds && d.p.seg_buf)
+      hipLaunchKernelGGL(k_pre_uv_segb, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp, t.nnew,
                          t.nrhs);
-    else if (d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp)
+    else if (lds)
       hipLaunchKernelGGL(k_pre_uv_seg<true>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp,
                          t.nnew, t.nrhs);
     else

@@ -42,27 +42,27 @@ __global__ void __launch_bounds__(256) k_step3d_t_h(Dev d, Range R, int nnew, in
 
 // The same for NTT <= 2 tracers with every global load issued at entry (see
 // k_pre_tracer_h1): one memory wait per block.  Bit-identical.
-template <int NTT, int TY>
+template <int NTT>
 struct TracerWinS {
-  static constexpr int kN = kUVW * (TY + 4);
+  static constexpr int kN = kUVW * (kBY + 4);
   double UM[kN], VM[kN], FU[kN], FV[kN], T[NTT][kN];
 };
-template <int NTT, int TY>
-__global__ void __launch_bounds__(kBX * TY) k_step3d_t_h1(Dev d, Range R, int nnew, int nrhs) {
-  const uint3 bI = h_tile(d.p.tile_grp);
-  __shared__ TracerWinS<NTT, TY> W;
+template <int NTT>
+__global__ void __launch_bounds__(kBX * kBY) k_step3d_t_h1(Dev d, Range R, int nnew, int nrhs) {
+  const uint3 bI = xcd_tile();
+  __shared__ TracerWinS<NTT> W;
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int k = 1 + (int)bI.z;
-  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * TY;
+  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * kBY;
   const int ib = i0 - 2, jb = j0 - 2;
   const long kk = (long)(k - 1) * b.n2;
   const int tid = threadIdx.x + kBX * threadIdx.y;
-  constexpr int NW = kUVW * (TY + 4), NR = (NW + kBX * TY - 1) / (kBX * TY);
+  constexpr int NW = kUVW * (kBY + 4), NR = (NW + kBX * kBY - 1) / (kBX * kBY);
   double wUM[NR], wVM[NR], wFU[NR], wFV[NR], wT[NTT][NR];
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     const int i = ib + q % kUVW, j = jb + q / kUVW;
     const bool ok = q < NW && i >= -1 && i <= b.Lm + 2 && j >= -1 && j <= b.Mm + 2;
     const long o = ok ? IJ(b, i, j) : 0;
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(kBX * TY) k_step3d_t_h1(Dev d, Range R, int nn
   for (int t = 0; t < NTT; t++) tn[t] = F.t[(long)(nnew - 1) * b.n3 + (long)t * 3 * b.n3 + o];
 #pragma unroll
   for (int r = 0; r < NR; r++) {
-    const int q = tid + r * kBX * TY;
+    const int q = tid + r * kBX * kBY;
     if (q < NW) {
       W.UM[q] = wUM[r]; W.VM[q] = wVM[r]; W.FU[q] = wFU[r]; W.FV[q] = wFV[r];
 #pragma unroll
@@ -367,20 +367,15 @@ __global__ void __launch_bounds__(kSegBlock, 2) k_step3d_t_seg(Dev d, Range R, i
   }
 }
 
-// ---- k_step3d_t_seg with buffer loads/stores (Params::seg_buf): a wave is
-// one segment, so its first cell c0 and row count n are wave-uniform
-// (readfirstlane); every level offset is then one SGPR shared by all fields
-// (soffset), the lane's column one VGPR (voffset), and no load carries a
-// 64-bit per-row address.  Same expressions in the same order: bitwise equal
-// to k_step3d_t_seg. ----
+// ---- k_step3d_t_seg with buffer loads/stores (Params::seg_buf): the lane's
+// column and the level offset in one VGPR (voffset), so no load carries a
+// 64-bit per-row address.  t(nnew) of the segment's rows (the diffusion
+// r.h.s.) is loaded at entry with the spline phase's inputs, so it lands
+// during its solve.  Same expressions in the same order: bitwise equal to
+// k_step3d_t_seg. ----
 #ifndef ROMS_SEG_T_GROUP
 #define ROMS_SEG_T_GROUP kSegLoadGroup
 #endif
-// PF: t(nnew) of the segment's rows (the diffusion r.h.s.) loaded at entry
-// with the spline phase's inputs, so they land during its solve.  RL: Hz
-// reloaded for the diffusion phase instead of kept live across the spline
-// solve (30 VGPRs at its register peak).
-template <bool PF, bool RL = false, bool UNI = true>
 __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(Dev d, Range R, int nnew, int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
   __shared__ SegXchg X;
@@ -390,15 +385,8 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
   const Params& P = d.p;
   const int N = b.N;
   const double dt = P.dt;
-  SegSpan sg = seg_span(N);
-  constexpr bool kU = UNI && kSegCW == kCX;   // scalar level offsets need one segment per wavefront
-  if constexpr (kU) seg_uniform(sg);
-  // UNI: level offsets in the SGPR soffset; else added to the VGPR offset
-  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return kU ? B.ld(v, l) : B.ld(v + l, 0u); };
-  auto ST = [&](const BufF64& B, double x, unsigned v, unsigned l) {
-    if constexpr (kU) B.st(x, v, l);
-    else B.st(x, v + l, 0u);   // v = kBufOff stays beyond the extent
-  };
+  const SegSpan sg = seg_span(N);
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
   const int iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
   const bool act = iu >= R.i0 && iu <= R.i1;
   const int i = act ? iu : (iu < R.i0 ? R.i0 : R.i1), j = R.j0 + (int)bI.y;
@@ -419,10 +407,8 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
     hz[q] = LD(Hz, vo, lev(c0 - 1 + q));
     if (q < KR) tt[q] = LD(Tr, vo, lev(c0 - 1 + q));
   }
-  if constexpr (PF) {
 #pragma unroll
-    for (int p = 0; p < KR; p++) tn[p] = LD(Tn, vo, lev(c0 + p));
-  }
+  for (int p = 0; p < KR; p++) tn[p] = LD(Tn, vo, lev(c0 + p));
   {
     double fc[KR];
     spline_fc_seg<KR>(sg, N, X, hz, tt, fc);
@@ -438,10 +424,6 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (RL) {
-#pragma unroll
-    for (int q = 0; q < KR + 1; q++) hz[q] = LD(Hz, vo, lev(c0 - 1 + q));
-  }
   const int iAkt = itrc < b.nTS ? itrc : b.nTS;
   const BufF64 Akt(F.Akt + (long)(iAkt - 1) * b.n3w);
   const BufF64 Pm(F.pm), Pn(F.pn);
@@ -456,7 +438,7 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
   double rhs[KR];
 #pragma unroll
   for (int p = 0; p < KR; p++)
-    rhs[p] = (PF ? tn[p] : LD(Tn, vo, lev(c0 + p))) - dt * pm * pn * (tt[p + 1 < KR ? p + 1 : KR - 1] - tt[p]);
+    rhs[p] = tn[p] - dt * pm * pn * (tt[p + 1 < KR ? p + 1 : KR - 1] - tt[p]);
   if (P.npip > 0) {   // pipe_frc.F sources (step3d_t_ISO.F:927-934)
     const int pidx = F.pipe_idx[ij];
     if (pidx > 0) {
@@ -551,7 +533,7 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
   // branch per row the compiler waited for every previous store before the
   // next one (vmcnt(0) at each branch join, 14 store round trips per wave)
 #pragma unroll
-  for (int p = 0; p < KR; p++) ST(Tn, T.D[p] * rm, p < n ? vs : kBufOff, lev(c0 + p));
+  for (int p = 0; p < KR; p++) Tn.st(T.D[p] * rm, (p < n ? vs : kBufOff) + lev(c0 + p), 0u);   // kBufOff stays beyond the extent
 }
 
 void setup_column_kernels_t(size_t bytes) {
@@ -582,14 +564,13 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
   }
   // horizontal fluxes, then the column solves, on a sub-range of the interior
   auto h_tiles = [&](const Range& r) {
-    if (d.p.hoist && b.NT == 2 && d.p.h_ty == 8)
-      hipLaunchKernelGGL((k_step3d_t_h1<2, 8>), grid3_ty(r, b.N, 8), dim3(kBX, 8), 0, s, d, r, t.nnew, t.nrhs);
-    else if (d.p.hoist && b.NT == 2)
-      hipLaunchKernelGGL((k_step3d_t_h1<2, 4>), grid3_ty(r, b.N, 4), dim3(kBX, 4), 0, s, d, r, t.nnew, t.nrhs);
+    const dim3 gh = grid3_of(r, b.N), bh(kBX, kBY);
+    if (d.p.hoist && b.NT == 2)
+      hipLaunchKernelGGL(k_step3d_t_h1<2>, gh, bh, 0, s, d, r, t.nnew, t.nrhs);
     else if (d.p.hoist && b.NT == 1)
-      hipLaunchKernelGGL((k_step3d_t_h1<1, 4>), grid3_ty(r, b.N, 4), dim3(kBX, 4), 0, s, d, r, t.nnew, t.nrhs);
+      hipLaunchKernelGGL(k_step3d_t_h1<1>, gh, bh, 0, s, d, r, t.nnew, t.nrhs);
     else
-      hipLaunchKernelGGL(k_step3d_t_h, grid3_of(r, b.N), dim3(kBX, kBY), 0, s, d, r, t.nnew, t.nrhs, 1);
+      hipLaunchKernelGGL(k_step3d_t_h, gh, bh, 0, s, d, r, t.nnew, t.nrhs, 1);
   };
   auto run = [&](const Range& r) {
     // horizontal advection: the rows strips cover (k_tracer_strip.hip), the rest on tiles
@@ -604,16 +585,8 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
     gt.z = b.NT;
     if (d.p.colseg) {
       ktimer_mark(s, kTimedStep3dTSeg, 0);
-      if ((d.p.seg_buf & 2) && (d.p.seg_buf & 8))
-        hipLaunchKernelGGL((k_step3d_t_segb<false, true>), seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r,
-                           t.nnew, t.nrhs);
-      else if ((d.p.seg_buf & 2) && (d.p.seg_buf & 4) && (d.p.seg_buf & 1024))
-        hipLaunchKernelGGL((k_step3d_t_segb<true, false, false>), seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d,
-                           r, t.nnew, t.nrhs);
-      else if ((d.p.seg_buf & 2) && (d.p.seg_buf & 4))
-        hipLaunchKernelGGL(k_step3d_t_segb<true>, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
-      else if (d.p.seg_buf & 2)
-        hipLaunchKernelGGL(k_step3d_t_segb<false>, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
+      if (d.p.seg_buf)
+        hipLaunchKernelGGL(k_step3d_t_segb, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
       else
         hipLaunchKernelGGL(k_step3d_t_seg, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
       ktimer_mark(s, kTimedStep3dTSeg, 1, 1);
@@ -626,23 +599,14 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
   auto edges = [&] {
     for (int itrc = 1; itrc <= b.NT; itrc++) launch_t3dbc(d, s, t, itrc);
   };
-  // Params::t_chunk: the horizontal part and the column solve alternate over
-  // strips of t_chunk rows (see launch_pre_step3d)
-  auto run_all = [&] {
-    if (d.p.t_chunk > 0 && d.p.colseg) {
-      for (int ja = R.j0; ja <= R.j1; ja += d.p.t_chunk) run(Range{R.i0, R.i1, ja, min(ja + d.p.t_chunk - 1, R.j1)});
-    } else {
-      run(R);
-    }
-  };
   ExchList L;
   if (!exchange) {   // t3dmix follows and exchanges t(nnew) itself
-    run_all();
+    run(R);
     edges();
   } else if (tracer_exch_list(d, t.nnew, L)) {
     launch_rim_first(d, s, R, L, run, edges);
   } else {
-    run_all();
+    run(R);
     edges();
     launch_exchange_tracers(d, s, t.nnew);
   }

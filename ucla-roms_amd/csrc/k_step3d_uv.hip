@@ -139,107 +139,6 @@ __global__ void __launch_bounds__(64) k_uv1(Dev d, Range R, int nnew, int nrhs) 
   }
 }
 
-// ---- register-resident variant of k_uv1 for a compile-time depth NN: one
-// of the two coefficient columns (the spline FC / Thomas DC, NN+1 doubles per
-// lane) lives in VGPRs, the other (CF) in LDS.  Every level loop is fully
-// unrolled, so each column element is a fixed register.  Half the LDS per
-// wave doubles the resident waves (6 per CU against 3 for the two-slot LDS
-// form at N = 50; both columns in VGPRs would spill).  Same expressions and
-// order as uv_vert_flux_lds<false> + uv1_col, so results are bit-identical. ----
-constexpr int kUv1Chunk = 5;
-template <int NN>
-__global__ void __launch_bounds__(64, 2) k_uv1_reg(Dev d, Range R, int nnew, int nrhs) {
-  ROMS_IJC_OR_RETURN(R)
-  col_lds_poison<ColLds>(1, NN);
-  const Bounds& b = d.b;
-  const Fields& F = d.f;
-  const int dir = (int)bI.z;
-  if (dir == 0 ? !(i >= b.istrU && i <= b.iend) : !(j >= b.jstrV)) return;
-  constexpr int N = NN;
-  const double dt = d.p.dt;
-  const long n2 = b.n2, ij = IJ(b, i, j);
-  const long s = dir == 0 ? 1 : b.nx2;
-  double A[N + 1];               // registers
-  const ColLds B = col_lds(0, N);  // LDS: 26 KB per wave at N = 50
-  uv_spline_reg<N>(d, ij, nrhs, dir, A, B);
-  double* __restrict__ Un = (dir == 0 ? F.u : F.v) + (long)(nnew - 1) * b.n3 + ij;
-  double* __restrict__ rr = (dir == 0 ? F.ru : F.rv) + ij;
-  const double* Hz = F.Hz + ij;
-  __asm__ volatile("" : "+v"(Hz));   // no reuse of the spline sweep's Hz loads
-  const double* __restrict__ Akv = F.Akv + ij;
-  const double* __restrict__ Wi = F.Wi + ij;
-  const double sstr = dir == 0 ? F.sustr[ij] : F.svstr[ij];
-  const double DC0 = dt * 0.25 * (F.pm[ij] + F.pm[ij - s]) * (F.pn[ij] + F.pn[ij - s]);
-  auto hz = [&](int k) { return Hz[(long)(k - 1) * n2]; };
-  auto hzm = [&](int k) { return Hz[(long)(k - 1) * n2 - s]; };
-  // pre-pass, k ascending, in chunks whose loads all precede their ru stores
-  // (inside the elimination every later ru load had to wait behind the
-  // previous level's store, may-alias): final ru(k) stored back, the Thomas
-  // right-hand side v(k) = u(nnew) + DC0*ru(k) kept in A[k-1] (A[k-1] is last
-  // read by ru(k)); ru(1) kept for rufrc.
-  double r1 = 0.0;
-#pragma unroll
-  for (int k0 = 1; k0 <= N; k0 += kUv1Chunk) {
-    double r_[kUv1Chunk], un_[kUv1Chunk];
-#pragma unroll
-    for (int q = 0; q < kUv1Chunk; q++) {
-      const long o = (long)(k0 + q - 1) * n2;
-      r_[q] = rr[o]; un_[q] = Un[o];
-    }
-#pragma unroll
-    for (int q = 0; q < kUv1Chunk; q++) {
-      const int k = k0 + q;
-      const double r = k == 1 ? r_[q] - A[1] : r_[q] - A[k] + A[k - 1];
-      rr[(long)(k - 1) * n2] = r;
-      if (k == 1) r1 = r;
-      A[k - 1] = un_[q] + DC0 * r;
-    }
-  }
-  double FCk = 2.0 * dt * (Akv[(long)(N - 1) * n2] + Akv[(long)(N - 1) * n2 - s]) /
-               (hz(N) + hzm(N) + hz(N - 1) + hzm(N - 1));
-  double WCk = DC0 * 0.5 * (Wi[(long)(N - 1) * n2] + Wi[(long)(N - 1) * n2 - s]);
-  double cff = 1.0 / (0.5 * (hz(N) + hzm(N)) + FCk - fmin0(WCk));
-  double CFk = cff * (FCk + fmax0(WCk));
-  double DCk1 = cff * (A[N - 1] + dt * sstr);
-  A[N] = DCk1;
-  B[N - 1] = CFk;
-#pragma unroll
-  for (int k = N - 1; k >= 2; k--) {
-    const double FCl = 2.0 * dt * (Akv[(long)(k - 1) * n2] + Akv[(long)(k - 1) * n2 - s]) /
-                       (hz(k) + hzm(k) + hz(k - 1) + hzm(k - 1));
-    const double WCl = DC0 * 0.5 * (Wi[(long)(k - 1) * n2] + Wi[(long)(k - 1) * n2 - s]);
-    cff = 1.0 / (0.5 * (hz(k) + hzm(k)) + FCl - fmin0(WCl) + FCk + fmax0(WCk) - CFk * (FCk - fmin0(WCk)));
-    const double CFl = cff * (FCl + fmax0(WCl));
-    const double DCk = cff * (A[k - 1] + DCk1 * (FCk - fmin0(WCk)));
-    B[k - 1] = CFl;
-    A[k] = DCk;
-    DCk1 = DCk; FCk = FCl; WCk = WCl; CFk = CFl;
-    ROMS_LEVEL_FENCE_AT(k);
-  }
-  const double rD = F.r_D[ij], rDm = F.r_D[ij - s];
-  double dc = (A[0] + DCk1 * (FCk - fmin0(WCk))) /
-              (0.5 * (hz(1) + hzm(1)) + 0.5 * dt * (rD + rDm) + FCk + fmax0(WCk) - CFk * (FCk - fmin0(WCk)));
-  Un[0] = dc * 0.5 * (hz(1) + hzm(1));
-  const double dmdn = dir == 0 ? F.dm_u[ij] * F.dn_u[ij] : F.dm_v[ij] * F.dn_v[ij];
-  double frc = r1 + dmdn * (sstr - 0.5 * (rDm + rD) * dc);
-  // reload Hz and ru in the back-substitution instead of keeping the N levels
-  // of the elimination sweep live in registers (laundered base pointers: the
-  // compiler may not forward the earlier loads / stores across the sweep)
-  const double* Hz2 = Hz;
-  const double* rr2 = rr;
-  __asm__ volatile("" : "+v"(Hz2), "+v"(rr2));
-#pragma unroll
-  for (int k = 2; k <= N; k++) {
-    dc = A[k] + B[k - 1] * dc;
-    const long o = (long)(k - 1) * n2;
-    Un[o] = dc * 0.5 * (Hz2[o] + Hz2[o - s]);
-    frc = frc + rr2[o];
-    ROMS_LEVEL_FENCE_AT(k);
-  }
-  if (dir == 0) F.rufrc[ij] = frc;
-  else F.rvfrc[ij] = frc;
-}
-
 // ---- segment-partitioned variant of k_uv1 (k_colseg.h) for deep grids:
 // block = kSegCW columns x S segments, grid z = direction.  Spline advection and
 // the implicit viscosity are each one partitioned tridiagonal system with the
@@ -407,13 +306,10 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_seg(Dev d, Rang
   }
 }
 
-// ---- k_uv1_seg<true> with buffer loads/stores (Params::seg_buf bit 32):
-// wave-uniform level offsets in SGPRs (seg_uniform), the lane's column and
-// its neighbour in VGPR offsets; PF: u(nnew) of the segment's rows loaded
-// with the spline phase's inputs.  Same expressions and order: bitwise equal
-// to k_uv1_seg<true>. ----
-// UNI false: the level offsets in the VGPR offset (no seg_uniform, no SGPR pressure)
-template <bool PF, bool UNI = true>
+// ---- k_uv1_seg<true> with buffer loads/stores (Params::seg_buf): the
+// lane's column and its neighbour, plus the level offset, in VGPR offsets
+// (no SGPR pressure).  Same expressions and order: bitwise equal to
+// k_uv1_seg<true>. ----
 __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Range R, int nnew, int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
   __shared__ SegXchg X;
@@ -423,9 +319,7 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
   const Fields& F = d.f;
   const int N = b.N;
   const double dt = d.p.dt;
-  SegSpan sg = seg_span(N);
-  constexpr bool kU = UNI && kSegCW == kCX;   // scalar level offsets need one segment per wavefront
-  if constexpr (kU) seg_uniform(sg);
+  const SegSpan sg = seg_span(N);
   SegCol col;
   seg_uv_col(d, R, bI, sg, col);
   if (col.idle) return;   // uniform over the block
@@ -440,13 +334,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
   double* const Sh = roms_smem + tid;                             // Hz(c0-1+q) at Sh[q*nthr]
   double* const Shm = roms_smem + (long)(KR + 1) * nthr + tid;    // its neighbour's at Shm[q*nthr]
   const BufF64 Un((dir == 0 ? F.u : F.v) + (long)(nnew - 1) * b.n3);
-  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return kU ? B.ld(v, l) : B.ld(v + l, 0u); };
-  double fl[KR], un[PF ? KR : 1];
-  if constexpr (PF) {
-#pragma unroll
-    for (int p = 0; p < KR; p++) un[p] = LD(Un, vo, lev(c0 + p));
-  }
-  uv_spline_segb<KR, kU>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned, double h0, double h1, double) {
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
+  double fl[KR];
+  uv_spline_segb<KR>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned, double h0, double h1, double) {
     Sh[q * nthr] = h0;
     Shm[q * nthr] = h1;
   });
@@ -489,7 +379,7 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
     const double b1 = 0.5 * (HZ(p + 1) + HZM(p + 1)) + 0.5 * dt * (rD + rDm) + fcu + fmax0(wcu);
     const double bk = 0.5 * (HZ(p + 1) + HZM(p + 1)) + fcl - fmin0(wcl) + fcu + fmax0(wcu);
     bb = k == 1 ? b1 : bk;
-    const double v = (PF ? un[p] : LD(Un, vo, lev(k))) + DC0 * rk[p];
+    const double v = LD(Un, vo, lev(k)) + DC0 * rk[p];
     dd = k == N ? v + dt * sstr : v;
     fcl = fcu; wcl = wcu;
   });
@@ -510,13 +400,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
     }
     __syncthreads();
   }
-  const unsigned vs = act ? vo : kBufOff;
 #pragma unroll
   for (int p = 0; p < KR; p++)
-    if (p < n) {
-      if constexpr (kU) Un.st(T.D[p] * 0.5 * (HZ(p + 1) + HZM(p + 1)), vs, lev(c0 + p));
-      else Un.st(T.D[p] * 0.5 * (HZ(p + 1) + HZM(p + 1)), act ? vo + lev(c0 + p) : kBufOff, 0u);
-    }
+    if (p < n) Un.st(T.D[p] * 0.5 * (HZ(p + 1) + HZM(p + 1)), act ? vo + lev(c0 + p) : kBufOff, 0u);
   if (act && sg.s == 0) {
     if (dir == 0) F.rufrc[ij] = Lf[S - 1][sl];
     else F.rvfrc[ij] = Lf[S - 1][sl];
@@ -534,13 +420,7 @@ void setup_uv1_seg() {
                             (int)((size_t)kSegRows * kSegMaxS * kSegCW * kSegJMax * sizeof(double)));
   (void)hipFuncSetAttribute((const void*)k_uv1_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_uv1_segb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_uv1_segb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_uv1_segb<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_uv1_segb<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)k_uv1_segb, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
 }
 
@@ -550,21 +430,11 @@ void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done)
   Range R{b.istr, b.iend, b.jstr, b.jend};
   dim3 g = gridc_of(R);
   g.z = 2;
-  if ((d.p.colreg & 1) && b.N == 50)
-    hipLaunchKernelGGL(k_uv1_reg<50>, g, dim3(kCX), col_lds_bytes(1, 50), s, d, R, t.nnew, t.nrhs);
-  else if (d.p.colseg) {
+  if (d.p.colseg) {
     const dim3 gs = seg_uv_grid(d, R, d.p.seg_jrows), bs(kCX, seg_waves(b.N), d.p.seg_jrows);
     ktimer_mark(s, kTimedUv1Seg, 0);
-    if (d.p.uv1_lds && d.p.uv_adv && (d.p.seg_buf & 32) && (d.p.seg_buf & 512) && (d.p.seg_buf & 64))
-      hipLaunchKernelGGL((k_uv1_segb<true, false>), gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew,
-                         t.nrhs);
-    else if (d.p.uv1_lds && d.p.uv_adv && (d.p.seg_buf & 32) && (d.p.seg_buf & 512))
-      hipLaunchKernelGGL((k_uv1_segb<false, false>), gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew,
-                         t.nrhs);
-    else if (d.p.uv1_lds && d.p.uv_adv && (d.p.seg_buf & 32) && (d.p.seg_buf & 64))
-      hipLaunchKernelGGL(k_uv1_segb<true>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
-    else if (d.p.uv1_lds && d.p.uv_adv && (d.p.seg_buf & 32))
-      hipLaunchKernelGGL(k_uv1_segb<false>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
+    if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf)
+      hipLaunchKernelGGL(k_uv1_segb, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
     else if (d.p.uv1_lds && d.p.uv_adv)
       hipLaunchKernelGGL(k_uv1_seg<true>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
     else

@@ -491,16 +491,11 @@ constexpr int kOmR = kSegRows;   // levels per wave (N <= kSegRows * kSegMaxS)
 // wavefront, several blocks per CU whose load and chain phases overlap;
 // 1.41 -> 1.24 ms per C3 call against 64, r5_w_omega_cw_par_ab.txt; level
 // offsets then go in the VGPR offset -- with SGPR offsets 32 columns had
-// measured 1.76 ms, r5_p_seg_cw32_ab.txt).  PAR (ROMS_GPU_OMEGA_PAR, opt-in):
-// each segment sums its own levels from zero while the others do, one
-// barrier, then adds the lower segments' totals in k order -- the chain of S
-// barrier steps becomes one (sums reassociated: not bitwise to PAR false;
-// no faster at 16 columns).
+// measured 1.76 ms, r5_p_seg_cw32_ab.txt).
 constexpr int kOmCW = kCX, kOmBlock = kSegMaxS * kOmCW;
-template <bool kHB, int CW = kOmCW, bool PAR = false>
+template <bool kHB, int CW = kOmCW>
 __global__ void __launch_bounds__(kSegMaxS * CW, 2) k_omega_seg(Dev d, Range R, double dtau, double hcff) {
-  // ROMS_GPU_OMEGA_ORD: the segment solvers' grouped block order (seg_tile)
-  const uint3 bI = d.p.omega_ord ? seg_tile(d.p.omega_ord, d.p.seg_xg) : xcd_tile();
+  const uint3 bI = xcd_tile();
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int N = b.N;
@@ -553,22 +548,6 @@ __global__ void __launch_bounds__(kSegMaxS * CW, 2) k_omega_seg(Dev d, Range R, 
   Lhz[s][l] = hz[0];
   // 1. the partial sums, wave by wave in k order
   double wk[kOmR];
-  if constexpr (PAR) {
-    double wi = 0.0;
-#pragma unroll
-    for (int q = 0; q < kOmR; q++) {
-      double v = wi - fu1[q] + fu0[q] - fv1[q] + fv0[q];
-      if (pidx > 0) v = v + pflx * prf[(long)(min(c0 + q, N) - 1) * d.p.npip];
-      wi = q < n ? v : wi;
-      wk[q] = wi;
-    }
-    Lw[s][l] = wi;
-    __syncthreads();
-    double base = 0.0;
-    for (int t = 0; t < s; t++) base = base + Lw[t][l];
-#pragma unroll
-    for (int q = 0; q < kOmR; q++) wk[q] = base + wk[q];
-  } else
   for (int t = 0; t < S; t++) {
     if (s == t) {
       double wi = t == 0 ? 0.0 : Lw[t - 1][l];
@@ -584,12 +563,7 @@ __global__ void __launch_bounds__(kSegMaxS * CW, 2) k_omega_seg(Dev d, Range R, 
     __syncthreads();
   }
   // 2. the Courant split of w-levels k = c0..c0+n-1 (k <= N-1)
-  double wtot = Lw[S - 1][l];
-  if constexpr (PAR) {
-    wtot = 0.0;
-    for (int t = 0; t < S; t++) wtot = wtot + Lw[t][l];
-  }
-  const double wrk = (wtot + wsrf) / (zwN - zw0);
+  const double wrk = (Lw[S - 1][l] + wsrf) / (zwN - zw0);
   const double cx_top = s + 1 < S ? Lcx[s + 1][l] : 0.0, hz_top = s + 1 < S ? Lhz[s + 1][l] : 0.0;
   if (!kHB && !act) return;
   const BufF64 Wi(F.Wi), We(F.We);
@@ -691,18 +665,15 @@ static size_t omega_hb_lds_bytes(unsigned nthr) { return (size_t)kOmR * nthr * s
 void setup_omega_seg() {
   (void)hipFuncSetAttribute((const void*)k_omega_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)omega_hb_lds_bytes(kOmBlock));
-  (void)hipFuncSetAttribute((const void*)k_omega_seg<true, kOmCW, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)omega_hb_lds_bytes(kOmBlock));
 }
 
-// k_omega_seg<kHB, CW, PAR> by ROMS_GPU_OMEGA_CW / ROMS_GPU_OMEGA_PAR
+// k_omega_seg<kHB, CW> by ROMS_GPU_OMEGA_CW
 template <bool kHB, int CW>
 static void omega_seg_cw(const Dev& d, hipStream_t s, const Range& r, double dtau, double hcff) {
   const Bounds& b = d.b;
   const dim3 gs((r.i1 - tile_i0(r.i0) + CW) / CW, r.j1 - r.j0 + 1), bs(kCX, seg_waves<CW>(b.N));
   const size_t lds = kHB ? omega_hb_lds_bytes(bs.x * bs.y) : 0;
-  if (d.p.omega_par) hipLaunchKernelGGL((k_omega_seg<kHB, CW, true>), gs, bs, lds, s, d, r, dtau, hcff);
-  else hipLaunchKernelGGL((k_omega_seg<kHB, CW, false>), gs, bs, lds, s, d, r, dtau, hcff);
+  hipLaunchKernelGGL((k_omega_seg<kHB, CW>), gs, bs, lds, s, d, r, dtau, hcff);
 }
 template <bool kHB>
 static void omega_seg(const Dev& d, hipStream_t s, const Range& r, double dtau, double hcff) {

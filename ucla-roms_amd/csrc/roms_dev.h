@@ -44,7 +44,8 @@ struct Bounds {
   int west_exch, east_exch, south_exch, north_exch;  // message edges (rank neighbours)
 };
 
-// Physics switches (cppdefs.opt) and scalars of the run.
+// Physics switches (cppdefs.opt), kernel-selection switches (ROMS_GPU_*,
+// roms_gpu_init) and scalars of the run.
 struct Params {
   int nonlin_eos, salinity, lmd, uv_vis2, ts_dif2;
   int lmd_rimix, lmd_convec, lmd_nonlocal;  // LMD_RIMIX, LMD_CONVEC, LMD_NONLOCAL (lmd != 0: MIXING+KPP+BKPP)
@@ -53,10 +54,11 @@ struct Params {
   int uv_adv, uv_cor;                       // UV_ADV, UV_COR
   int tides;                                // TIDES pot_tides: ptide in prsgrd
   int bulk_frc;                             // BULK_FRC (k_bulk.hip; u* from sustr_r/svstr_r in lmd_kpp)
-  int prs_split;                            // 1: two-kernel prsgrd (default), 0: k_prsgrd_fused (ROMS_GPU_PRSGRD_FUSED=1)
+  // ---- kernel selection: the form of a routine, never its result ----
+  int prs_split;  // 1: two-kernel prsgrd (default), 0: k_prsgrd_fused (ROMS_GPU_PRSGRD_FUSED=1)
   int s2d_split;  // 1: step2d as separate zeta / momentum kernels (ROMS_GPU_S2D_SPLIT=1)
   int colseg;     // 1: segment-partitioned column solvers (k_colseg.h; N > 63, ROMS_GPU_COLSEG=0/1)
-  int colreg;     // 1: register-resident column solvers where compiled for N (ROMS_GPU_COLREG=0 disables)
+  int colreg;     // bit 2: register-resident k_pre_tracer_v_reg where compiled for N (ROMS_GPU_COLREG=0: the LDS form)
   int uv2_fused;  // 1: one-pass step3d_uv2 (k_uv2_fused; ROMS_GPU_UV2_FUSED=0 disables)
   int chain;      // 1: chained 4-lane set_HUV1 (k_chain.h; ROMS_GPU_CHAIN=0 disables)
   int seg_order;  // block order of the segment solvers (seg_tile; ROMS_GPU_SEG_ORDER)
@@ -65,29 +67,28 @@ struct Params {
   int hoist;        // per-level horizontal kernels with every global load at entry (ROMS_GPU_HOIST=0: per-phase forms)
   int chain_dirz;   // chain kernels (set_HUV1, uv2): one direction per block (ROMS_GPU_CHAIN_DIRZ=0: both in turn)
   int prs_fuse_uv;  // whole steps: horizontal momentum r.h.s. inside prsgrd (ROMS_GPU_PRS_UV=0: separate)
-  int h_ty;       // tile rows of the hoisted horizontal kernels: 4 or 8 (ROMS_GPU_HTY)
-  int h_jc;       // rows per block of the j-marching horizontal kernels (multiple of 4; ROMS_GPU_HJC, 0: 64 x h_ty tiles)
-  int prs_ty;     // tile rows of k_prsgrd_uv: 4 or 8 (ROMS_GPU_PRS_TY)
-  int ld16;       // padded pitch: LDS windows read two doubles per lane (16-B loads; ROMS_GPU_LD16=0: 8-B)
+  int h_jc;       // rows per block of the j-marching horizontal kernels (multiple of 4; ROMS_GPU_HJC, 0: 64 x 4 tiles)
   int prs_buf;    // k_prsgrd_uv windows through buffer loads (ROMS_GPU_PRS_BUF)
   int prs_strip;  // prsgrd + momentum r.h.s. in j-marching strips (k_prsgrd_strip; ROMS_GPU_PRS_STRIP=0: tiles)
   int t_strip;    // horizontal tracer advection in j-marching strips (k_tracer_strip; ROMS_GPU_T_STRIP=0: tiles)
   int visc_stg;   // visc3d: raw u/v/Hz windows staged in LDS per level (default; ROMS_GPU_VISC_STG=0: per-point loads)
   int t3dmix_stg; // t3dmix (two tracers): Hz/T/S windows staged in LDS per level (default; ROMS_GPU_T3DMIX_STG=0: per-point loads)
   int kpp_ty;     // k_kpp_int: 4 (default) staged Rig windows on 64x4 blocks, 8 on 64x8, 43 64x4 at 3 waves/SIMD, 0 one row per block (ROMS_GPU_KPP_TY)
-  int tile_grp;   // h_tile group width of the hoisted per-level kernels (ROMS_GPU_TILE_GRP; 0: xcd_tile order)
   int uv1_lds;    // k_uv1_seg: Hz pairs kept in LDS from the spline phase, rufrc chained (ROMS_GPU_UV1_LDS=0: reloads)
   int omega_seg;  // omega: segment form k_omega_seg, one read of each input (ROMS_GPU_OMEGA_SEG=0: two-pass k_omega)
   int omega_cw;   // k_omega_seg columns per block: 64, 32 or 16 (ROMS_GPU_OMEGA_CW)
-  int omega_ord;  // k_omega_seg block order: 0 xcd_tile, 1..3 seg_tile's orders (ROMS_GPU_OMEGA_ORD)
-  int omega_par;  // k_omega_seg: segment partial sums in parallel, one barrier (ROMS_GPU_OMEGA_PAR; not bitwise to the k-order chain)
   int p_in_rho;   // rho_eos's sweep also forms prsgrd's P (ROMS_GPU_P_IN_RHO=0: k_prsgrd_P)
   int omega_hb;   // the predictor's omega forms pre_step3d's Hz_bak/Hz_fwd (ROMS_GPU_OMEGA_HB=0: pre_step3d does)
   int preuv_lds;  // k_pre_uv_seg: u(indx) stored and u(nstp)/u(indx) combined in the spline phase (ROMS_GPU_PREUV_LDS=0: reloads)
   int seg_jrows;  // rows j per block of the momentum segment solvers (1..kSegJMax; ROMS_GPU_SEG_JROWS)
-  int t_chunk;    // tracer horizontal part + column solve alternating over strips of t_chunk rows (ROMS_GPU_TCHUNK; 0: off)
-  int seg_buf;    // segment solvers with buffer loads, wave-uniform level offsets (ROMS_GPU_SEG_BUF bits)
-  int seg_vtile;  // v columns of the momentum segment solvers on 16 x 4 tiles per wavefront (ROMS_GPU_SEG_VTILE=0: rows of 64)
+  int seg_buf;    // 1: segment solvers with buffer loads (k_*_segb; ROMS_GPU_SEG_BUF=0: the pointer forms)
+  // eight retired switches stood among the ints above: their room stays, so
+  // that every member from here on -- and Fields after Params -- keeps its
+  // kernel-argument offset (without it lmd_vmix measured 2-3% slower at C3,
+  // its kernels differing in nothing but their scalar-load offsets:
+  // profiles/r9_retire_variants_ab.txt)
+  int reserved_[8];
+  // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
   int npip;       // pipe_frc.F: number of pipes (0: pipe_source off)
@@ -270,31 +271,6 @@ __device__ __forceinline__ uint3 xcd_tile() {
   t.x = logical % gx;
   t.y = (logical / gx) % gy;
   t.z = logical / (gx * gy);
-  return t;
-}
-
-// Per-level horizontal kernels with halo windows: xcd_tile()'s sequence
-// re-ordered within each level (z) so that y runs fastest inside groups of
-// grp x-tiles (grp <= 0: plain xcd_tile order).  The tiles resident on one
-// XCD then cover a grp-wide strip of consecutive rows, whose shared halo
-// rows (j-neighbours) and halo lines (i-neighbours inside the group) are
-// fetched by neighbours close together in time.
-__device__ __forceinline__ uint3 h_tile(int grp) {
-  uint3 t = xcd_tile();
-  if (grp <= 0) return t;
-  const unsigned gx = gridDim.x, gy = gridDim.y;
-  const unsigned L = t.x + gx * t.y;
-  const unsigned G = (unsigned)grp < gx ? (unsigned)grp : gx;
-  const unsigned nfull = gx / G, inf = nfull * G * gy;
-  if (L < inf) {
-    const unsigned rem = L % (G * gy);
-    t.x = (L / (G * gy)) * G + rem % G;
-    t.y = rem / G;
-  } else {
-    const unsigned Gl = gx - nfull * G, rem = L - inf;
-    t.x = nfull * G + rem % Gl;
-    t.y = rem / Gl;
-  }
   return t;
 }
 
@@ -514,8 +490,8 @@ void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up = -1, b
 // j-marching strips (mode 0 step3d_t, 1 pre_step3d); false: not covered
 bool launch_tracer_strip(const Dev& d, hipStream_t s, const Range& R, int mode, bool up, bool hb_done, int nnew,
                          int nrhs, double dtau, double cf_stp, double cf_bak, int nstp, int& jA, int& jB);
-bool p_in_rho(const Dev& d);   // every rho_eos also forms prsgrd's P (k_vertical.hip)
-void launch_prsgrd_P(const Dev& d, hipStream_t s);   // prsgrd's P alone (k_prsgrd_P)
+bool p_in_rho(const Dev& d);
+void launch_prsgrd_P(const Dev& d, hipStream_t s);   // prsgrd's P alone (k_prsgrd_P)   // every rho_eos also forms prsgrd's P (k_vertical.hip)
 bool prsgrd_can_fuse_uv(const Dev& d);
 // A second stream for work with no data dependence on the main stream's
 // (enqueue_step, single rank): the callee forks `s2` off `s` with `efork`

@@ -215,6 +215,24 @@ int post_launch() {
   return 0;
 }
 
+// ROMS_GPU_* switches (roms_gpu_init): a default-on switch is turned off by a
+// value starting with '0', a default-off one on by a value starting with '1'
+bool env_off(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
+bool env_on(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
+}
+// an integer in lo..hi; def when unset, not a number or out of range
+int env_int(const char* name, int def, int lo, int hi) {
+  const char* e = getenv(name);
+  if (!e || !((e[0] >= '0' && e[0] <= '9') || (e[0] == '-' && e[1] >= '0' && e[1] <= '9'))) return def;
+  const int v = atoi(e);
+  return v >= lo && v <= hi ? v : def;
+}
+
 Bounds make_bounds(const roms_dims& D, int pitch, int gx = 0) {
   Bounds b{};
   b.Lm = D.Lm; b.Mm = D.Mm; b.N = D.N; b.NT = D.NT;
@@ -789,8 +807,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   {
     // device row pitch: Lm+4 rounded up to 128 B, base shifted so that i = 1
     // starts a line (roms_dev.h); ROMS_GPU_PITCH=0 keeps the host layout
-    const char* e = getenv("ROMS_GPU_PITCH");
-    const bool pad = !(e && e[0] == '0');
+    const bool pad = !env_off("ROMS_GPU_PITCH");
     const int hx = dims->Lm + 4;
     // Multi-rank runs: the barotropic fast loop exchanges zeta/ubar/vbar
     // every s2d_k fast steps over 2*s2d_k-wide halos and recomputes the
@@ -802,11 +819,8 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     // GPU with every exchange self-addressed through IPC (C2, 92 exchanges
     // per step at K = 1): 7.48 / 7.11 / 7.01 / 6.98 ms per step at K = 1..4
     // against 6.49 without a communicator (profiles/r4_j_fast_exchange_interval_ab.txt).
-    int k = 4;
-    const char* ek = getenv("ROMS_GPU_S2D_K");   // 1..8 (an interconnect slower than one GPU's may want 6-8)
-    if (ek && atoi(ek) >= 1 && atoi(ek) <= 8) k = atoi(ek);
-    const char* es = getenv("ROMS_GPU_S2D_SPLIT");
-    const bool split = es && es[0] == '1';
+    int k = env_int("ROMS_GPU_S2D_K", 4, 1, 8);   // (an interconnect slower than one GPU's may want 6-8)
+    const bool split = env_on("ROMS_GPU_S2D_SPLIT");
     const int obc = cfg->obc & ((dims->ew_periodic ? 0 : 3) | (dims->ns_periodic ? 0 : 12));
     // every rank decides alike, from the global sizes: the 2k-wide strips
     // (and the 2(k-1) cells a widened fast step reaches into its neighbour)
@@ -849,19 +863,13 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   P.tides = cfg->pot_tides != 0;
   P.bulk_frc = cfg->bulk_frc != 0;
   P.iso = cfg->adv_isoneutral != 0;
-  {
-    // fused one-kernel prsgrd (k_prsgrd_fused): bit-identical, fewer bytes,
-    // but measured slower at C2 (0.50 vs 0.38 ms per call: a per-level walk
-    // of 2 blocks per CU hides less latency than the level-parallel grid)
-    // and only 4% faster at C3 -- opt-in, ROMS_GPU_PRSGRD_FUSED=1
-    const char* e = getenv("ROMS_GPU_PRSGRD_FUSED");
-    P.prs_split = !(e && e[0] == '1');
-  }
+  // fused one-kernel prsgrd (k_prsgrd_fused): bit-identical, fewer bytes,
+  // but measured slower at C2 (0.50 vs 0.38 ms per call: a per-level walk
+  // of 2 blocks per CU hides less latency than the level-parallel grid)
+  // and only 4% faster at C3 -- opt-in, ROMS_GPU_PRSGRD_FUSED=1
+  P.prs_split = !env_on("ROMS_GPU_PRSGRD_FUSED");
   P.uv_vis2 = cfg->uv_vis2; P.ts_dif2 = cfg->ts_dif2;
-  {
-    const char* e = getenv("ROMS_GPU_S2D_SPLIT");
-    P.s2d_split = e && e[0] == '1';
-  }
+  P.s2d_split = env_on("ROMS_GPU_S2D_SPLIT");
   P.dt = cfg->dt; P.dtfast = cfg->dt / (double)cfg->ndtfast; P.g = cfg->g; P.rho0 = cfg->rho0;
   P.vonKar = 0.41; P.qp2 = 0.0000172; P.gamma2 = cfg->gamma2; P.hc = cfg->hc;
   P.rdrg = cfg->rdrg; P.Zob = cfg->Zob; P.Tcoef = cfg->Tcoef; P.T0 = cfg->T0; P.Scoef = cfg->Scoef; P.S0 = cfg->S0;
@@ -882,234 +890,98 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   // (every segment must hold at least kSegNMin rows: seg_rows_ok, k_colseg.h)
   const bool seg_fits = dims->N <= kSegRows * kSegMaxS && seg_rows_ok(dims->N);
   P.colseg = (size_t)2 * (dims->N + 1) * kCX * sizeof(double) > 64 * 1024 && seg_fits;
-  {
-    const char* e = getenv("ROMS_GPU_COLSEG");
-    if (e && e[0] == '0') P.colseg = 0;
-    if (e && e[0] == '1') P.colseg = seg_fits;
-  }
-  // register-resident sequential solvers (bit-exact) for the depths they are
-  // compiled for; ROMS_GPU_COLREG=0 falls back to the LDS form (A/B runs)
-  // bits: 1 step3d_uv1 (k_uv1_reg), 2 pre_step3d tracers (k_pre_tracer_v_reg);
-  // ROMS_GPU_COLREG=<mask> (0: the LDS forms).  Measured at C2 (round 2):
-  // bit 2 pre_step3d 2.06 -> 1.96 ms; bit 1 step3d_uv1 1.23 ms against 1.16
-  // for the LDS form, so bit 1 is off by default.  (The LDS form once failed
-  // the C2 100-step parity test in some test-process histories: that was the
-  // zero fill of a new model's arrays racing with its first kernels, see
-  // dev_alloc, not the solver; both forms are equal bitwise.)  Register
-  // forms of pre_uv_col (2.06 -> 2.20 ms) and k_step3d_t_v (its extra
-  // per-level KPP inputs spill at 2 waves/SIMD; 0.84 vs 0.81 ms at 1
-  // wave/SIMD) were slower and are not kept.
-  P.colreg = 2;
-  {
-    const char* e = getenv("ROMS_GPU_COLREG");
-    if (e && e[0] >= '0' && e[0] <= '9') P.colreg = atoi(e);
-  }
-  P.uv2_fused = 1;
-  {
-    const char* e = getenv("ROMS_GPU_UV2_FUSED");
-    if (e && e[0] == '0') P.uv2_fused = 0;
-  }
-  P.chain = 1;
-  {
-    const char* e = getenv("ROMS_GPU_CHAIN");
-    if (e && e[0] == '0') P.chain = 0;
-  }
+  if (env_off("ROMS_GPU_COLSEG")) P.colseg = 0;
+  if (env_on("ROMS_GPU_COLSEG")) P.colseg = seg_fits;
+  // register-resident sequential solver of pre_step3d's tracers
+  // (k_pre_tracer_v_reg, bit 2; bit-exact) for the depths it is compiled for;
+  // ROMS_GPU_COLREG=0 falls back to the LDS form.  Measured at C2 (round 2):
+  // pre_step3d 2.06 -> 1.96 ms.  Register forms of step3d_uv1 (1.23 against
+  // 1.16 ms for the LDS form), pre_uv_col (2.06 -> 2.20 ms) and k_step3d_t_v
+  // (its extra per-level KPP inputs spill at 2 waves/SIMD; 0.84 vs 0.81 ms at
+  // 1 wave/SIMD) were slower and are not kept.
+  P.colreg = env_int("ROMS_GPU_COLREG", 2, 0, 3);
+  P.uv2_fused = !env_off("ROMS_GPU_UV2_FUSED");
+  P.chain = !env_off("ROMS_GPU_CHAIN");
   // order 3 in groups of 8 x-blocks: on 16-column blocks the resident
   // blocks of an XCD then cover 8 x 16 columns of consecutive rows, sharing
   // their i- and j-neighbour lines in L2 (pre_step3d 9.81-9.84 -> 9.61-9.65
   // ms, step3d_uv1 3.92-3.94 -> 3.81-3.83 ms per C3 call against order 0,
   // r5_x_seg_order_ab.txt)
-  P.seg_order = 3;
-  {
-    const char* e = getenv("ROMS_GPU_SEG_ORDER");
-    if (e && e[0] >= '0' && e[0] <= '3') P.seg_order = e[0] - '0';
-  }
-  P.seg_xg = 8;
-  {
-    const char* e = getenv("ROMS_GPU_SEG_XG");
-    if (e && atoi(e) > 0) P.seg_xg = atoi(e);
-  }
-  {
-    const char* e = getenv("ROMS_GPU_S2D_EDGES");
-    P.s2d_fold = !(e && e[0] == '1');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_CHAIN_DIRZ");
-    P.chain_dirz = !(e && e[0] == '0');   // set_HUV1 2.55 -> 2.03 ms at C3 (r3_s_chain_dirz_ab.txt)
-  }
-  {
-    const char* e = getenv("ROMS_GPU_PRS_UV");
-    P.prs_fuse_uv = !(e && e[0] == '0');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_TILE_GRP");
-    P.tile_grp = e ? atoi(e) : 0;
-  }
-  {
-    const char* e = getenv("ROMS_GPU_UV1_LDS");
-    P.uv1_lds = !(e && e[0] == '0');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_P_IN_RHO");
-    P.p_in_rho = !(e && e[0] == '0');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_OMEGA_HB");
-    P.omega_hb = !(e && e[0] == '0');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_OMEGA_SEG");
-    P.omega_seg = !(e && e[0] == '0');
-  }
+  P.seg_order = env_int("ROMS_GPU_SEG_ORDER", 3, 0, 3);
+  P.seg_xg = env_int("ROMS_GPU_SEG_XG", 8, 1, 1 << 30);
+  P.s2d_fold = !env_on("ROMS_GPU_S2D_EDGES");
+  P.chain_dirz = !env_off("ROMS_GPU_CHAIN_DIRZ");   // set_HUV1 2.55 -> 2.03 ms at C3 (r3_s_chain_dirz_ab.txt)
+  P.prs_fuse_uv = !env_off("ROMS_GPU_PRS_UV");
+  P.uv1_lds = !env_off("ROMS_GPU_UV1_LDS");
+  P.p_in_rho = !env_off("ROMS_GPU_P_IN_RHO");
+  P.omega_hb = !env_off("ROMS_GPU_OMEGA_HB");
+  P.omega_seg = !env_off("ROMS_GPU_OMEGA_SEG");
   {
     // 16-column blocks (four segments per wavefront, 4 blocks per CU) with
-    // the k-order chain: omega 1.41 -> 1.24 ms per C3 call, as fast as the
-    // parallel partial sums and bitwise to the 64-column form
-    // (r5_w_omega_cw_par_ab.txt)
+    // the k-order chain: omega 1.41 -> 1.24 ms per C3 call, bitwise to the
+    // 64-column form (r5_w_omega_cw_par_ab.txt)
     // (at N <= 63, C2, 64 columns stay: 0.161 against 0.167 ms per call)
-    const char* e = getenv("ROMS_GPU_OMEGA_CW");
-    const int v = e ? atoi(e) : (dims->N > 63 ? 16 : 64);
+    const int v = env_int("ROMS_GPU_OMEGA_CW", dims->N > 63 ? 16 : 64, 0, 1 << 30);
     P.omega_cw = v == 32 || v == 64 ? v : 16;
-    e = getenv("ROMS_GPU_OMEGA_ORD");
-    P.omega_ord = e && e[0] >= '1' && e[0] <= '3' ? e[0] - '0' : 0;
-    e = getenv("ROMS_GPU_OMEGA_PAR");
-    P.omega_par = e && e[0] == '1';
   }
-  {
-    const char* e = getenv("ROMS_GPU_PREUV_LDS");
-    P.preuv_lds = !(e && e[0] == '0');
-  }
-  {
-    const char* e = getenv("ROMS_GPU_HTY");
-    P.h_ty = (e && atoi(e) == 8) ? 8 : 4;
-  }
-  {
-    // j-marching per-level horizontal kernels: rows per block (ROMS_GPU_HJC;
-    // 0 = off, the default: k_pre_tracer_hj measured slower at C3, 12.15 ->
-    // 12.65 ms per pre_step3d, r4c: the 64 x 4 tiles' j-halo rows are mostly
-    // L2 hits already (PMC 16.2 passes against 14), and the ring's in-flight
-    // rows and lanes halve the waves per SIMD)
-    const char* e = getenv("ROMS_GPU_HJC");
-    P.h_jc = 0;
-    if (e && atoi(e) >= 0) P.h_jc = atoi(e) / 4 * 4;
-  }
-  {
-    const char* e = getenv("ROMS_GPU_PRS_TY");
-    P.prs_ty = (e && atoi(e) == 8) ? 8 : 4;
-  }
-  {
-    // 16-B window loads (they need every row's i0-2 on a 16-B boundary: the
-    // padded device pitch, g.off, gives that, roms_dev.h) measured slower at
-    // C3 (k_prsgrd_uv 4.20-4.26 vs 3.96 ms per call, same box, the 8-B form
-    // with a 67-wide window 3.6 ms): opt-in, ROMS_GPU_LD16=1
-    const char* e = getenv("ROMS_GPU_LD16");
-    P.ld16 = g.off != 0 && e && e[0] == '1';
-  }
-  {
-    // visc3d with staged raw windows (bitwise): C3 2.34 -> 1.94 ms, C2 0.35 -> 0.30 ms
-    // (r3_zq_visc_stg_ab.txt); ROMS_GPU_VISC_STG=0 for per-point loads
-    const char* e = getenv("ROMS_GPU_VISC_STG");
-    P.visc_stg = !(e && e[0] == '0');
-  }
-  {
-    // t3dmix with staged windows (bitwise): C3 1.65 -> 1.31 ms, C2 0.218 -> 0.145 ms
-    // (r3_zs_t3dmix_stg_ab.txt); ROMS_GPU_T3DMIX_STG=0 for per-point loads
-    const char* e = getenv("ROMS_GPU_T3DMIX_STG");
-    P.t3dmix_stg = !(e && e[0] == '0');
-  }
+  P.preuv_lds = !env_off("ROMS_GPU_PREUV_LDS");
+  // j-marching per-level horizontal kernels: rows per block (ROMS_GPU_HJC;
+  // 0 = off, the default: k_pre_tracer_hj measured slower at C3, 12.15 ->
+  // 12.65 ms per pre_step3d, r4c: the 64 x 4 tiles' j-halo rows are mostly
+  // L2 hits already (PMC 16.2 passes against 14), and the ring's in-flight
+  // rows and lanes halve the waves per SIMD)
+  P.h_jc = env_int("ROMS_GPU_HJC", 0, 0, 1 << 30) / 4 * 4;
+  // visc3d with staged raw windows (bitwise): C3 2.34 -> 1.94 ms, C2 0.35 -> 0.30 ms
+  // (r3_zq_visc_stg_ab.txt); ROMS_GPU_VISC_STG=0 for per-point loads
+  P.visc_stg = !env_off("ROMS_GPU_VISC_STG");
+  // t3dmix with staged windows (bitwise): C3 1.65 -> 1.31 ms, C2 0.218 -> 0.145 ms
+  // (r3_zs_t3dmix_stg_ab.txt); ROMS_GPU_T3DMIX_STG=0 for per-point loads
+  P.t3dmix_stg = !env_off("ROMS_GPU_T3DMIX_STG");
   {
     // staged Rig windows in k_kpp_int (bitwise): lmd_vmix 3.49 -> 3.22 ms per
     // call at C3 (r3_zp_kpp_ty_ab.txt); ROMS_GPU_KPP_TY=0 for one row per block
-    const char* e = getenv("ROMS_GPU_KPP_TY");
-    P.kpp_ty = 4;
-    if (e && (atoi(e) == 0 || atoi(e) == 2 || atoi(e) == 8 || atoi(e) == 43)) P.kpp_ty = atoi(e);
+    const int v = env_int("ROMS_GPU_KPP_TY", 4, 0, 43);
+    P.kpp_ty = v == 0 || v == 2 || v == 8 || v == 43 ? v : 4;
   }
-  {
-    // lmd_vmix without the work past the boundary layers (bitwise; the bits
-    // in roms_dev.h); ROMS_GPU_KPP_LEAN=0 for the full forms, 1..7 for a
-    // subset of the three parts.  ROMS_GPU_KPP_FCKEEP=1..kKppFcKeepMax: levels
-    // above FC(0) that k_kpp_ext keeps in LDS
-    const char* e = getenv("ROMS_GPU_KPP_LEAN");
-    P.kpp_lean = 7;
-    if (e && e[0] >= '0' && e[0] <= '7' && e[1] == 0) P.kpp_lean = e[0] - '0';
-    const char* k = getenv("ROMS_GPU_KPP_FCKEEP");
-    P.kpp_fckeep = kKppFcKeepMax;
-    if (k && atoi(k) >= 1 && atoi(k) <= kKppFcKeepMax) P.kpp_fckeep = atoi(k);
-  }
-  {
-    // Hz, z_r, z_w formed in the kernel from z_sd, h, hinv (VGrid, bitwise; the
-    // bits in roms_dev.h); ROMS_GPU_VGRID=0 for the streaming forms, 1..15 a
-    // set of kernels.  Default 11: k_kpp_int (bit 4) is slower with it
-    const char* e = getenv("ROMS_GPU_VGRID");
-    P.vgrid = kVgDefault;
-    if (e && e[0] >= '0' && e[0] <= '9' && atoi(e) >= 0 && atoi(e) <= kVgAll) P.vgrid = (short)atoi(e);
-    P.vg = 0;
-    g.vgrid_valid = false;
-  }
-  {
-    const char* e = getenv("ROMS_GPU_HOIST");
-    P.hoist = !(e && e[0] == '0');
-  }
-  {
-    // default on: C3 prsgrd 3.62-3.63 -> 3.55 ms per call (r5_d_seg_buf_chunk_prs_ab.txt)
-    const char* e = getenv("ROMS_GPU_PRS_BUF");
-    P.prs_buf = !(e && e[0] == '0');
-  }
-  {
-    // prsgrd's ru/rv with the momentum r.h.s. in j-marching strips (one
-    // evaluation per face, neighbours through DPP lane shifts; bitwise equal
-    // to the k_prsgrd_uv tiles); ROMS_GPU_PRS_STRIP=0: tiles everywhere
-    const char* e = getenv("ROMS_GPU_PRS_STRIP");
-    P.prs_strip = !(e && e[0] == '0');
-  }
-  {
-    // horizontal tracer advection of pre_step3d / step3d_t in j-marching
-    // strips (k_tracer_strip, bitwise equal to the k_*_h1 tiles): measured
-    // slower at C3 (pre_step3d 9.65 -> 10.56, step3d_t 4.75 -> 5.66 ms per
-    // call, profiles/r6_e_tracer_strip_ab.txt: too little arithmetic per row
-    // to cover each row's loads), so opt-in, ROMS_GPU_T_STRIP=1
-    const char* e = getenv("ROMS_GPU_T_STRIP");
-    P.t_strip = e && e[0] == '1';
-  }
-  {
-    const char* e = getenv("ROMS_GPU_TCHUNK");
-    P.t_chunk = e ? atoi(e) : 0;
-    if (P.t_chunk < 0) P.t_chunk = 0;
-  }
-  {
-    const char* e = getenv("ROMS_GPU_SEG_BUF");
-    // bits: 1 k_pre_tracer_segb, 2 k_step3d_t_segb, 4 its t(nnew) prefetch,
-    // 8 its Hz reload, 16 k_pre_tracer_segb's prefetch, 32 k_uv1_segb, 64 its
-    // u(nnew) prefetch, 128 k_pre_uv_segb, 256 its Hz_fwd prefetch, 512 the
-    // momentum solvers' buffer forms without seg_uniform (level offsets in
-    // the VGPR offset), 1024 the same for the tracer solvers.  Default 679
-    // (7 + the momentum solvers' buffer forms with VGPR level offsets):
-    // pre_step3d 11.24-11.31 -> 10.88-11.08 ms, step3d_uv1 4.63 -> 4.50-4.53
-    // (profiles/r5_l_seg_buf_vgpr_ab.txt)  Default 7: C3
-    // 57.4-57.7 -> 56.7 ms/step, step3d_t 5.98 -> 5.75 ms, pre_step3d
-    // 11.5 -> 11.3 ms (same box, profiles/r5_c_seg_buf_ab.txt); the momentum
-    // solvers' buffer forms (32, 128, + prefetch) measured slower (step3d_uv1
-    // 4.6 -> 6.0-6.6 ms, pre_step3d +0.3-2.1 ms: r5_d_seg_buf_chunk_prs_ab.txt)
-    P.seg_buf = e ? atoi(e) : 679;
-  }
-  {
-    const char* e = getenv("ROMS_GPU_SEG_VTILE");
-    P.seg_vtile = !(e && e[0] == '0');
-  }
-  P.seg_jrows = kSegJMax < 2 ? kSegJMax : 2;
-  {
-    const char* e = getenv("ROMS_GPU_SEG_JROWS");
-    if (e && atoi(e) >= 1 && atoi(e) <= kSegJMax) P.seg_jrows = atoi(e);
-  }
+  // lmd_vmix without the work past the boundary layers (bitwise; the bits
+  // in roms_dev.h); ROMS_GPU_KPP_LEAN=0 for the full forms, 1..7 for a
+  // subset of the three parts.  ROMS_GPU_KPP_FCKEEP=1..kKppFcKeepMax: levels
+  // above FC(0) that k_kpp_ext keeps in LDS
+  P.kpp_lean = (short)env_int("ROMS_GPU_KPP_LEAN", 7, 0, 7);
+  P.kpp_fckeep = (short)env_int("ROMS_GPU_KPP_FCKEEP", kKppFcKeepMax, 1, kKppFcKeepMax);
+  // Hz, z_r, z_w formed in the kernel from z_sd, h, hinv (VGrid, bitwise; the
+  // bits in roms_dev.h); ROMS_GPU_VGRID=0 for the streaming forms, 1..15 a
+  // set of kernels.  Default 11: k_kpp_int (bit 4) is slower with it
+  P.vgrid = (short)env_int("ROMS_GPU_VGRID", kVgDefault, 0, kVgAll);
+  P.vg = 0;
+  g.vgrid_valid = false;
+  P.hoist = !env_off("ROMS_GPU_HOIST");
+  // default on: C3 prsgrd 3.62-3.63 -> 3.55 ms per call (r5_d_seg_buf_chunk_prs_ab.txt)
+  P.prs_buf = !env_off("ROMS_GPU_PRS_BUF");
+  // prsgrd's ru/rv with the momentum r.h.s. in j-marching strips (one
+  // evaluation per face, neighbours through DPP lane shifts; bitwise equal
+  // to the k_prsgrd_uv tiles); ROMS_GPU_PRS_STRIP=0: tiles everywhere
+  P.prs_strip = !env_off("ROMS_GPU_PRS_STRIP");
+  // horizontal tracer advection of pre_step3d / step3d_t in j-marching
+  // strips (k_tracer_strip, bitwise equal to the k_*_h1 tiles): measured
+  // slower at C3 (pre_step3d 9.65 -> 10.56, step3d_t 4.75 -> 5.66 ms per
+  // call, profiles/r6_e_tracer_strip_ab.txt: too little arithmetic per row
+  // to cover each row's loads), so opt-in, ROMS_GPU_T_STRIP=1
+  P.t_strip = env_on("ROMS_GPU_T_STRIP");
+  // the segment solvers' buffer forms (k_pre_tracer_segb, k_step3d_t_segb with
+  // its t(nnew) prefetch, k_uv1_segb, k_pre_uv_segb; level offsets in the VGPR
+  // offset); ROMS_GPU_SEG_BUF=0: the pointer forms.  Tracers: C3 57.4-57.7 ->
+  // 56.7 ms/step, step3d_t 5.98 -> 5.75 ms, pre_step3d 11.5 -> 11.3 ms
+  // (profiles/r5_c_seg_buf_ab.txt); momentum: pre_step3d 11.24-11.31 ->
+  // 10.88-11.08 ms, step3d_uv1 4.63 -> 4.50-4.53 (profiles/r5_l_seg_buf_vgpr_ab.txt)
+  P.seg_buf = !env_off("ROMS_GPU_SEG_BUF");
+  P.seg_jrows = env_int("ROMS_GPU_SEG_JROWS", kSegJMax < 2 ? kSegJMax : 2, 1, kSegJMax);
   // column-solver scratch: LDS while two (N+1)-level slots per wave fit the
   // default 64 KB (N < 63), global memory for deeper grids;
   // ROMS_GPU_COL_GLOBAL=1/0 forces either (A/B runs)
   bool col_global = (size_t)2 * (dims->N + 1) * kCX * sizeof(double) > 64 * 1024;
-  {
-    const char* e = getenv("ROMS_GPU_COL_GLOBAL");
-    if (e && e[0] == '1') col_global = true;
-    if (e && e[0] == '0') col_global = false;
-  }
+  if (env_on("ROMS_GPU_COL_GLOBAL")) col_global = true;
+  if (env_off("ROMS_GPU_COL_GLOBAL")) col_global = false;
   setup_uv1_seg();
   setup_pre_uv_seg();
   setup_omega_seg();
@@ -1125,15 +997,11 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     // step, profiles/r4_j_two_stream_ab.txt): the concurrent kernels compete
     // for CUs and LDS (the segment solvers hold one block per CU), so the
     // second stream is opt-in, ROMS_GPU_PAR=1
-    const char* e = getenv("ROMS_GPU_PAR");
     const char* em = getenv("ROMS_GPU_PAR_MASK");
-    g.par = e && e[0] == '1' ? 31 : 0;
+    g.par = env_on("ROMS_GPU_PAR") ? 31 : 0;
     if (em) g.par = atoi(em) & 31;
   }
-  {
-    const char* e = getenv("ROMS_GPU_GUARD");
-    g.guard = e && e[0] == '1';
-  }
+  g.guard = env_on("ROMS_GPU_GUARD");
   const Bounds& b = g.d.b;
   // the 2-D fields first and next to each other (then the 2-D scratch), so
   // that the fast step's fields share one buffer window (S2dWin below)
@@ -1183,7 +1051,6 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     // the fast step's buffer window (k_s2d_fb): every field's origin IJ = -lead
     // and its last element within 2 GiB of one base; else (or with
     // ROMS_GPU_S2D_WIN=0) the kernel addresses them through their pointers
-    const char* e = getenv("ROMS_GPU_S2D_WIN");
     g.d.w2 = S2dWin{};
     const double* wp[kWinN] = {F.zeta,  F.ubar,  F.vbar,    F.h,       F.dn_u,    F.dm_v,       F.pm,
                                F.pn,    F.swflx, F.rmask,   F.rhoS,    F.rhoA,    F.umask,      F.vmask,
@@ -1196,7 +1063,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
       lo = std::min(lo, (uintptr_t)wp[f] - (uintptr_t)lead * 8u);
       hi = std::max(hi, (uintptr_t)wp[f] + (uintptr_t)cnt * 8u);
     }
-    if (!(e && e[0] == '0') && hi - lo < (uintptr_t)2147483648u - (1u << 20)) {
+    if (!env_off("ROMS_GPU_S2D_WIN") && hi - lo < (uintptr_t)2147483648u - (1u << 20)) {
       g.d.w2.base = (const double*)lo;
       g.d.w2.lead = (int)lead;
       for (int f = 0; f < kWinN; f++) g.d.w2.off[f] = (unsigned)((uintptr_t)wp[f] - (uintptr_t)lead * 8u - lo);
@@ -1222,9 +1089,8 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     // uv2 3.93 -> 3.39 ms, step 60.8 -> 59.7 ms same box
     // (profiles/r4_p_uv2_edge_colreg_ab.txt); ROMS_GPU_UV2_EDGE=0: the
     // one-lane edge mode
-    const char* e = getenv("ROMS_GPU_UV2_EDGE");
     std::vector<int> lc, lf;
-    if (!(e && e[0] == '0')) uv2_edge_lists(b, lc, lf);
+    if (!env_off("ROMS_GPU_UV2_EDGE")) uv2_edge_lists(b, lc, lf);
     if (!lc.empty() && !lf.empty()) {
       CHECK_HIP(hipMalloc(&F.uv2e_couple, lc.size() * sizeof(int)));
       CHECK_HIP(hipMalloc(&F.uv2e_flux, lf.size() * sizeof(int)));
@@ -1253,15 +1119,10 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     g.halo.ls = g.s;
     g.d.halo = &g.halo;
   }
-  {
-    const char* e = getenv("ROMS_GPU_HZ_UV");
-    g.hzuv_env = e && e[0] == '1';
-    g.hzuv_valid = true;
-  }
-  const char* env = getenv("ROMS_GPU_NO_GRAPH");
-  g.use_graphs = !(env && env[0] == '1') && halo_graph_safe(g.d.halo);
-  env = getenv("ROMS_GPU_RHO_REUSE");
-  g.rho_reuse = !(env && env[0] == '0');
+  g.hzuv_env = env_on("ROMS_GPU_HZ_UV");
+  g.hzuv_valid = true;
+  g.use_graphs = !env_on("ROMS_GPU_NO_GRAPH") && halo_graph_safe(g.d.halo);
+  g.rho_reuse = !env_off("ROMS_GPU_RHO_REUSE");
   g.rho_slot = 0;
   g.inited = true;
   return 0;
