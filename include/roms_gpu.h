@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 20
+#define ROMS_GPU_ABI_VERSION 21
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -335,11 +335,17 @@ int roms_gpu_kpp_lean(void);
  * streams the arrays again until the next set_depth -- a host that supplies
  * its own Hz keeps the reference's semantics.
  * roms_gpu_vgrid returns mask + 256 * valid, negative before init.
+ * ROMS_GPU_VGRID2 (read at init; a mask, default 31, 0 for the streaming forms) is the same switch, under
+ * the same validity, for further kernels that walk a column or stage a level:
+ *   1  k_omega_seg   2  k_set_huv1_chain   4  k_uv2_fused   8  k_visc3d_stg
+ *   16 k_t3dmix_stg
+ * roms_gpu_vgrid2 returns that mask + 256 * valid, negative before init.
  * roms_gpu_vgrid_check compares the stored z_w, z_r, Hz with the values formed
  * from the kept surface as bit patterns, over set_depth's range and the
  * exchanged or wrapped halos; out[0..2] = mismatches of z_w, z_r, Hz (all 0
  * whenever the grid is valid).                                              */
 int roms_gpu_vgrid(void);
+int roms_gpu_vgrid2(void);
 int roms_gpu_vgrid_check(long out[3]);
 /* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
  * edges and the ROMS_GPU_* switches by the same host functions the launchers

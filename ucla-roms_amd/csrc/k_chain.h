@@ -21,6 +21,10 @@ namespace roms {
 
 constexpr int kChainCW = 16;   // columns per wavefront
 constexpr int kChainG = 4;     // segments (lanes) per column
+// levels whose loads are in flight together in the VGrid forms' load loops, as in
+// the streaming forms (13 measured no better: k_uv2_fused 1.64-1.65 against
+// 1.60-1.61 ms per C3 call, profiles/r10_vgrid_rest_ab.txt)
+constexpr int kChainVgGroup = 8;
 
 struct ChainLane {
   int col, g;    // column in the wavefront's row, segment (0 = bottom)

@@ -678,7 +678,14 @@ __global__ void __launch_bounds__(256) k_t3dmix(Dev d, Range R, int nnew, int nr
 // registers (about 5 loads per lane per level for the stencils instead of
 // 15); the per-tracer expressions of k_t3dmix, bit-identical.  Lanes past
 // the range walk the levels too (barriers) and store nothing.
+// VG (Params::vg bit kVg2T3dmix): a thread's Hz entries of the window (its
+// first kTMG entries can be) keep z_sd, h, hinv and the running z_w(k-1) of
+// their cell and form level k+1's Hz where ldw loads it otherwise; the level is
+// block-uniform, so Cs_w(k+1) is a scalar load, issued a level ahead.  Entries
+// outside set_depth's range and its halos form a value nothing consumes.
 constexpr int kTMW = kBX + 2, kTMN = kTMW * (kBY + 2), kTMQ = (3 * kTMN + kBX * kBY - 1) / (kBX * kBY);
+constexpr int kTMG = (kTMN + kBX * kBY - 1) / (kBX * kBY);
+template <bool VG>
 __global__ void __launch_bounds__(256) k_t3dmix_stg(Dev d, Range R, int nnew, int nrhs) {
   const uint3 bI = xcd_tile();
   __shared__ double sW[3 * kTMN];   // Hz, T, S
@@ -717,11 +724,38 @@ __global__ void __launch_bounds__(256) k_t3dmix_stg(Dev d, Range R, int nnew, in
     wf[m] = ok ? f : -1;
     wo[m] = ok ? IJ(b, ii, jj) : 0;
   }
+  double gz[kTMG], gh[kTMG], gi[kTMG], gw[kTMG];   // VG: z_sd, h, hinv, z_w(k-1) of the Hz entries' cells
+  double csw = 0.0;                                // VG: Cs_w of the level ldw forms next
+  if constexpr (VG) {
+#pragma unroll
+    for (int m = 0; m < kTMG; m++) {
+      const bool hzm = wf[m] == 0;
+      gz[m] = hzm ? F.z_sd[wo[m]] : 0.0;
+      gh[m] = hzm ? F.h[wo[m]] : 0.0;
+      gi[m] = hzm ? F.hinv[wo[m]] : 0.0;
+      gw[m] = -gh[m];   // VGrid::zw0
+    }
+    csw = F.Cs_w[1];
+  }
   auto ldw = [&](int k, double (&x)[kTMQ]) {
     const long kk = (long)(k - 1) * n2;
+    const double cs = csw;
+    if constexpr (VG) csw = F.Cs_w[min(k + 1, b.N)];
+    if constexpr (VG) {   // the T, S loads first: the Hz entries' arithmetic runs under them
 #pragma unroll
-    for (int m = 0; m < kTMQ; m++)
-      x[m] = wf[m] == 0 ? F.Hz[wo[m] + kk] : wf[m] == 1 ? Tr[0][wo[m] + kk] : wf[m] == 2 ? Tr[1][wo[m] + kk] : 0.0;
+      for (int m = 0; m < kTMQ; m++) x[m] = wf[m] == 1 ? Tr[0][wo[m] + kk] : wf[m] == 2 ? Tr[1][wo[m] + kk] : 0.0;
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int m = 0; m < kTMG; m++) {
+        const double z = vg_make(d, gz[m], gh[m], gi[m]).zw1(k, cs);
+        x[m] = wf[m] == 0 ? z - gw[m] : x[m];
+        gw[m] = z;
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < kTMQ; m++)
+        x[m] = wf[m] == 0 ? F.Hz[wo[m] + kk] : wf[m] == 1 ? Tr[0][wo[m] + kk] : wf[m] == 2 ? Tr[1][wo[m] + kk] : 0.0;
+    }
   };
   const int c = (threadIdx.x + 1) + (threadIdx.y + 1) * kTMW;   // the lane's cell in the window
   double w[kTMQ];
@@ -756,7 +790,9 @@ void launch_t3dmix(const Dev& d, hipStream_t s, const Tlev& t) {
   Range R{b.istr, b.iend, b.jstr, b.jend};
   const bool stg = d.p.t3dmix_stg && b.NT == 2;
   auto run = [&](const Range& r) {
-    if (stg) hipLaunchKernelGGL(k_t3dmix_stg, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nnew, t.nrhs);
+    if (stg && (d.p.vg & (kVg2T3dmix << kVg2Shift)))
+      hipLaunchKernelGGL(k_t3dmix_stg<true>, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nnew, t.nrhs);
+    else if (stg) hipLaunchKernelGGL(k_t3dmix_stg<false>, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nnew, t.nrhs);
     else hipLaunchKernelGGL(k_t3dmix, grid_of(r), dim3(kBX, kBY), 0, s, d, r, t.nnew, t.nrhs);
   };
   ExchList L;

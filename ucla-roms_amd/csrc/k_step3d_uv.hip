@@ -617,11 +617,22 @@ __global__ void __launch_bounds__(256) k_visc3d(Dev d, Range R, int nstp) {
 constexpr int kVUW = kBX + 3, kVUN = kVUW * (kBY + 2);   // u window
 constexpr int kVVW = kBX + 2, kVVN = kVVW * (kBY + 3);   // v window
 constexpr int kVHW = kBX + 2, kVHN = kVHW * (kBY + 2);   // Hz window
+// VG (Params::vg bit kVg2Visc): a thread's Hz entries of the raw window (its
+// entries kVG0.. can be) keep z_sd, h, hinv and the running z_w(k-1) of their
+// cell and form level k+1's Hz where ldraw loads it otherwise; the level is
+// block-uniform, so Cs_w(k+1) is a scalar load, issued a level ahead.  The four
+// values per cell sit in LDS (sG, each slot written and read by its own thread
+// only: no barrier; in registers the kernel spilled at 3 waves per SIMD).
+// Entries outside set_depth's range and its halos form a value nothing consumes.
 constexpr int kVSN = kVUN + kVVN + kVHN, kVSQ = (kVSN + kBX * kBY - 1) / (kBX * kBY);
+constexpr int kVG0 = (kVUN + kVVN) / (kBX * kBY);
+constexpr int kVGS = kVHN + 1;   // sG's stride: slot kVHN is read by the entries that are not Hz
+template <bool VG>
 __global__ void __launch_bounds__(256, 3) k_visc3d_stg(Dev d, Range R, int nstp) {
   const uint3 bI = xcd_tile();
   __shared__ double sUFx[kVN], sVFe[kVN], sUFe[kVN], sVFx[kVN];
   __shared__ double sRaw[kVSN];
+  __shared__ double sG[VG ? 4 * kVGS : 1];   // z_sd, h, hinv, z_w(k-1) of the Hz window's cells
   const Bounds& b = d.b;
   const Fields& F = d.f;
   const int indx = 3 - nstp;
@@ -677,11 +688,50 @@ __global__ void __launch_bounds__(256, 3) k_visc3d_stg(Dev d, Range R, int nstp)
     wf[m] = f;
     wo[m] = f >= 0 ? IJ(b, ii, jj) : 0;
   }
+  double csw = 0.0;   // VG: Cs_w of the level ldraw forms next
+  if constexpr (VG) {
+#pragma unroll
+    for (int m = kVG0; m < kVSQ; m++) {
+      const int hq = tid + m * kBX * kBY - (kVUN + kVVN);
+      if (hq >= 0 && hq < kVHN) {
+        const bool on = wf[m] == 2;
+        const double h = on ? F.h[wo[m]] : 0.0;
+        sG[hq] = on ? F.z_sd[wo[m]] : 0.0;
+        sG[kVGS + hq] = h;
+        sG[2 * kVGS + hq] = on ? F.hinv[wo[m]] : 0.0;
+        sG[3 * kVGS + hq] = -h;   // VGrid::zw0
+      }
+    }
+    if (tid == 0) sG[kVHN] = sG[kVGS + kVHN] = sG[2 * kVGS + kVHN] = sG[3 * kVGS + kVHN] = 0.0;
+    csw = F.Cs_w[1];
+  }
   auto ldraw = [&](int k, double (&x)[kVSQ]) {
     const long kk = (long)(k - 1) * b.n2;
+    const double cs = csw;
+    if constexpr (VG) csw = F.Cs_w[min(k + 1, b.N)];
+    double hzv[kVSQ - kVG0 > 0 ? kVSQ - kVG0 : 1];
+    if constexpr (VG) {   // first, so that nothing of it is live beside the loads' addresses
 #pragma unroll
-    for (int m = 0; m < kVSQ; m++)
-      x[m] = wf[m] == 0 ? U[wo[m] + kk] : wf[m] == 1 ? V[wo[m] + kk] : wf[m] == 2 ? F.Hz[wo[m] + kk] : 0.0;
+      for (int m = kVG0; m < kVSQ; m++) {
+        const int hq = tid + m * kBX * kBY - (kVUN + kVVN);
+        const int hs = hq >= 0 && hq < kVHN ? hq : kVHN;   // kVHN: the slot of the entries that are not Hz (never consumed)
+        const double z = vg_make(d, sG[hs], sG[kVGS + hs], sG[2 * kVGS + hs]).zw1(k, cs);
+        hzv[m - kVG0] = z - sG[3 * kVGS + hs];
+        sG[3 * kVGS + hs] = z;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int m = 0; m < kVSQ; m++) {
+      if (VG && m >= kVG0) {
+        const double hz = hzv[m - kVG0];
+        // (no u entry from kVG0 on, and a v entry in the first of them only)
+        if (m * kBX * kBY < kVUN + kVVN) x[m] = wf[m] == 1 ? V[wo[m] + kk] : wf[m] == 2 ? hz : 0.0;
+        else x[m] = wf[m] == 2 ? hz : 0.0;
+      } else {
+        x[m] = wf[m] == 0 ? U[wo[m] + kk] : wf[m] == 1 ? V[wo[m] + kk] : !VG && wf[m] == 2 ? F.Hz[wo[m] + kk] : 0.0;
+      }
+    }
   };
   auto Uw = [&](int ii, int jj) { return sRaw[(ii - (i0 - 1)) + (jj - (j0 - 1)) * kVUW]; };
   auto Vw = [&](int ii, int jj) { return sRaw[kVUN + (ii - (i0 - 1)) + (jj - (j0 - 1)) * kVVW]; };
@@ -765,8 +815,10 @@ __global__ void __launch_bounds__(256, 3) k_visc3d_stg(Dev d, Range R, int nstp)
 void launch_visc3d(const Dev& d, hipStream_t s, const Tlev& t) {
   const Bounds& b = d.b;
   Range R{b.istr, b.iend, b.jstr, b.jend};
-  if (d.p.visc_stg)
-    hipLaunchKernelGGL(k_visc3d_stg, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nstp);
+  if (d.p.visc_stg && (d.p.vg & (kVg2Visc << kVg2Shift)))
+    hipLaunchKernelGGL(k_visc3d_stg<true>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nstp);
+  else if (d.p.visc_stg)
+    hipLaunchKernelGGL(k_visc3d_stg<false>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nstp);
   else
     hipLaunchKernelGGL(k_visc3d, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nstp);
 }
@@ -919,7 +971,9 @@ __global__ void __launch_bounds__(256) k_uv2_flux(Dev d, Range R, int nnew, int 
 // 256-thread blocks per CU keep the same occupancy
 // FULL: N == 4*KL, every segment holds KL levels (C3's N = 100), so the
 // per-level guards fold away and the level loops are straight-line code
-template <int KL, bool FULL = false>
+// VG (Params::vg bit kVg2Uv2): Hz of the column and of its i-1 / j-1
+// neighbour from two VGrid columns, as k_set_huv1_chain<.., VG> forms them
+template <int KL, bool FULL = false, bool VG = false>
 __global__ void __launch_bounds__(256, KL > 13 ? 3 : 4) k_uv2_fused(Dev d, Range R, int nnew, int nstp, int knew) {
   constexpr bool kHcLds = KL > 13;
   __shared__ double sHc[kHcLds ? KL * 256 : 1];
@@ -967,12 +1021,33 @@ __global__ void __launch_bounds__(256, KL > 13 ? 3 : 4) k_uv2_fused(Dev d, Range
       double* r;
       __device__ __forceinline__ double& operator[](int q) const { return kHcLds ? l[q * 256] : r[q]; }
     } const hc{sHc + threadIdx.x, hcr};
+    if constexpr (VG) {
+      const VGrid g0 = vg_column(d, ij), gm = vg_column(d, ij - s);
+      // opaque per direction: the levels' constants and Cs_w are the same for
+      // both, and hoisted out of the direction loop they held 100 VGPRs
+      int lv = lo;
+      __asm__ volatile("" : "+v"(lv));
+      const int kb = min(lv, N) - 1;   // the w-level below the lane's first, 0..N-1
+      const double csb = F.Cs_w[kb];
+      double w0 = g0.zw(kb, csb), wm = gm.zw(kb, csb);
 #pragma unroll
-    for (int q = 0; q < KL; q++) {
-      un[q] = bUn.ld(vq(q), so(q));
-      hc[q] = 0.5 * (bHz.ld(vq(q), so(q)) + bHz.ld(vqm(q), so(q)));
-      // the loads of 8 levels in flight at a time (all 25 hoisted spilled)
-      if (q % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+      for (int q = 0; q < KL; q++) {
+        const int k = min(lv + q, N);
+        const double cs = F.Cs_w[k];
+        un[q] = bUn.ld(vq(q), so(q));
+        const double z0 = g0.zw1(k, cs), zm = gm.zw1(k, cs);
+        hc[q] = 0.5 * ((z0 - w0) + (zm - wm));
+        w0 = z0; wm = zm;
+        if (q % kChainVgGroup == kChainVgGroup - 1) __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < KL; q++) {
+        un[q] = bUn.ld(vq(q), so(q));
+        hc[q] = 0.5 * (bHz.ld(vq(q), so(q)) + bHz.ld(vqm(q), so(q)));
+        // the loads of 8 levels in flight at a time (all 25 hoisted spilled)
+        if (q % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+      }
     }
     // k_uv2_couple: CF0 = sum Hz_u, DC0 = sum Hz*u (k = N..1); u = Hz*u/Hz_u
     double CF0, DC0;
@@ -1157,10 +1232,15 @@ void launch_step3d_uv2(const Dev& d, hipStream_t s, const Tlev& t) {
   if (!d.p.obc && d.p.uv2_fused && kl <= 25) {
     dim3 gf = chain_grid_of(R1);
     gf.z = d.p.chain_dirz ? 2 : 1;
-    if (kl <= 5) hipLaunchKernelGGL(k_uv2_fused<5>, gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
-    else if (kl <= 13) hipLaunchKernelGGL(k_uv2_fused<13>, gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
-    else if (b.N == 100) hipLaunchKernelGGL((k_uv2_fused<25, true>), gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
-    else hipLaunchKernelGGL(k_uv2_fused<25>, gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
+    const bool vg = (d.p.vg & (kVg2Uv2 << kVg2Shift)) != 0;
+    auto fused = [&](auto kern, auto kern_vg) {
+      if (vg) hipLaunchKernelGGL(kern_vg, gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
+      else hipLaunchKernelGGL(kern, gf, dim3(256), 0, s, d, R1, t.nnew, t.nstp, t.knew);
+    };
+    if (kl <= 5) fused(k_uv2_fused<5>, k_uv2_fused<5, false, true>);
+    else if (kl <= 13) fused(k_uv2_fused<13>, k_uv2_fused<13, false, true>);
+    else if (b.N == 100) fused(k_uv2_fused<25, true>, k_uv2_fused<25, true, true>);
+    else fused(k_uv2_fused<25>, k_uv2_fused<25, false, true>);
     if (d.f.uv2e_couple && d.p.uv2e_nc > 0 && d.p.uv2e_nf > 0) {   // closed edges: chain form over the column lists
       const int nc = d.p.uv2e_nc, nf = d.p.uv2e_nf;
       const dim3 gc((nc + 63) / 64), gf2((nf + 63) / 64);

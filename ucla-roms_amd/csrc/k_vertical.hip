@@ -236,7 +236,12 @@ __global__ void __launch_bounds__(256) k_set_huv1(Dev d, Range R, int nnew, int 
 // dropped), so the loops are straight-line code.  FULL: N == 4*KL (C3).
 // KL > 13: the lane's Hz_u*dn levels sit in LDS (as k_uv2_fused's Hz_u), so
 // the block fits 4 waves per SIMD in registers
-template <int KL, bool FULL = false>
+// VG (Params::vg bit kVg2Huv1): Hz of the column and of its i-1 / j-1
+// neighbour from two VGrid columns, each one's z_w carried up the lane's KL
+// levels; Cs_w of the lane's level is a per-lane table read (four segments
+// per wavefront), clamped to N in an empty or short segment, whose values
+// are ignored as the streamed zeros are.
+template <int KL, bool FULL = false, bool VG = false>
 __global__ void __launch_bounds__(256, KL > 13 ? 3 : 4) k_set_huv1_chain(Dev d, Range R, int nnew, int first) {
   constexpr bool kDcLds = KL > 13;
   __shared__ double sDc[kDcLds ? KL * 256 : 1];
@@ -271,11 +276,32 @@ __global__ void __launch_bounds__(256, KL > 13 ? 3 : 4) k_set_huv1_chain(Dev d, 
       double* r;
       __device__ __forceinline__ double& operator[](int q) const { return kDcLds ? l[q * 256] : r[q]; }
     } const dc{sDc + threadIdx.x, dcr};
+    if constexpr (VG) {
+      const VGrid g0 = vg_column(d, ij), gm = vg_column(d, ij - s);
+      // opaque per direction: the levels' constants and Cs_w are the same for
+      // both, and hoisted out of the direction loop they held 100 VGPRs
+      int lo = cl.lo;
+      __asm__ volatile("" : "+v"(lo));
+      const int kb = min(lo, N) - 1;   // the w-level below the lane's first, 0..N-1
+      const double csb = F.Cs_w[kb];
+      double w0 = g0.zw(kb, csb), wm = gm.zw(kb, csb);
 #pragma unroll
-    for (int q = 0; q < KL; q++) {
-      uu[q] = bU.ld(vq(q), so(q));
-      dc[q] = 0.5 * (bHz.ld(vq(q), so(q)) + bHz.ld(vqm(q), so(q))) * dn;
-      if (q % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+      for (int q = 0; q < KL; q++) {
+        const int k = min(lo + q, N);
+        const double cs = F.Cs_w[k];
+        uu[q] = bU.ld(vq(q), so(q));
+        const double z0 = g0.zw1(k, cs), zm = gm.zw1(k, cs);
+        dc[q] = 0.5 * ((z0 - w0) + (zm - wm)) * dn;
+        w0 = z0; wm = zm;
+        if (q % kChainVgGroup == kChainVgGroup - 1) __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < KL; q++) {
+        uu[q] = bU.ld(vq(q), so(q));
+        dc[q] = 0.5 * (bHz.ld(vq(q), so(q)) + bHz.ld(vqm(q), so(q))) * dn;
+        if (q % 8 == 7) __builtin_amdgcn_sched_barrier(0);
+      }
     }
     double DC0, FC0;
     chain_down(cl, DC0, FC0, [&](double& a, double& c) {
@@ -308,11 +334,15 @@ void launch_set_huv1(const Dev& d, hipStream_t s, const Tlev& t) {
   const int kl = chain_kl(b.N), first = (int)(t.iic == t.forw_start);
   dim3 gc = chain_grid_of(R);
   gc.z = d.p.chain_dirz ? 2 : 1;
-  if (d.p.chain && kl == 5) hipLaunchKernelGGL(k_set_huv1_chain<5>, gc, dim3(256), 0, s, d, R, t.nnew, first);
-  else if (d.p.chain && kl == 13) hipLaunchKernelGGL(k_set_huv1_chain<13>, gc, dim3(256), 0, s, d, R, t.nnew, first);
-  else if (d.p.chain && kl == 25 && b.N == 100)
-    hipLaunchKernelGGL((k_set_huv1_chain<25, true>), gc, dim3(256), 0, s, d, R, t.nnew, first);
-  else if (d.p.chain && kl == 25) hipLaunchKernelGGL(k_set_huv1_chain<25>, gc, dim3(256), 0, s, d, R, t.nnew, first);
+  const bool vg = (d.p.vg & (kVg2Huv1 << kVg2Shift)) != 0;
+  auto chain = [&](auto kern, auto kern_vg) {
+    if (vg) hipLaunchKernelGGL(kern_vg, gc, dim3(256), 0, s, d, R, t.nnew, first);
+    else hipLaunchKernelGGL(kern, gc, dim3(256), 0, s, d, R, t.nnew, first);
+  };
+  if (d.p.chain && kl == 5) chain(k_set_huv1_chain<5>, k_set_huv1_chain<5, false, true>);
+  else if (d.p.chain && kl == 13) chain(k_set_huv1_chain<13>, k_set_huv1_chain<13, false, true>);
+  else if (d.p.chain && kl == 25 && b.N == 100) chain(k_set_huv1_chain<25, true>, k_set_huv1_chain<25, true, true>);
+  else if (d.p.chain && kl == 25) chain(k_set_huv1_chain<25>, k_set_huv1_chain<25, false, true>);
   else hipLaunchKernelGGL(k_set_huv1, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nnew, first);
   launch_exchange_list(d, s, ExchList{{d.f.FlxU, d.f.FlxV, d.f.u + (long)(t.nnew - 1) * b.n3,
                                         d.f.v + (long)(t.nnew - 1) * b.n3}, {b.N, b.N, b.N, b.N}, 4});
@@ -492,8 +522,13 @@ constexpr int kOmR = kSegRows;   // levels per wave (N <= kSegRows * kSegMaxS)
 // 1.41 -> 1.24 ms per C3 call against 64, r5_w_omega_cw_par_ab.txt; level
 // offsets then go in the VGPR offset -- with SGPR offsets 32 columns had
 // measured 1.76 ms, r5_p_seg_cw32_ab.txt).
+// VG (Params::vg bit kVg2Omega): the lane's Hz and z_w rows, z_w(0) and
+// z_w(N) from VGrid.  z_w is carried over the segment's rows (Hz(k) = z_w(k)
+// - z_w(k-1): one more z_w than rows), and the rows' Cs_w -- a per-lane table
+// read, the level differs over the lanes of a wavefront of four segments --
+// are loaded at entry with the fluxes.  A clamped row (past N) repeats row N.
 constexpr int kOmCW = kCX, kOmBlock = kSegMaxS * kOmCW;
-template <bool kHB, int CW = kOmCW>
+template <bool kHB, int CW = kOmCW, bool VG = false>
 __global__ void __launch_bounds__(kSegMaxS * CW, 2) k_omega_seg(Dev d, Range R, double dtau, double hcff) {
   const uint3 bI = xcd_tile();
   const Bounds& b = d.b;
@@ -521,15 +556,37 @@ __global__ void __launch_bounds__(kSegMaxS * CW, 2) k_omega_seg(Dev d, Range R, 
   __shared__ double Lw[kSegMaxS][CW], Lcx[kSegMaxS][CW], Lhz[kSegMaxS][CW];
   __shared__ double Lte[kHB ? kSegMaxS : 1][CW], Lti[kHB ? kSegMaxS : 1][CW];   // kHB: segment tops' We, Wi
   double fu1[kOmR], fu0[kOmR], fv1[kOmR], fv0[kOmR], cx[kOmR], hz[kOmR], zk[kOmR];
+  const int kb = min(c0, N) - 1;   // VG: the w-level below the first row, 0..N-1
+  const double csb = VG ? F.Cs_w[kb] : 0.0, csN = VG ? F.Cs_w[N] : 0.0;
 #pragma unroll
   for (int q = 0; q < kOmR; q++) {   // rho level k = c0+q (clamped), w-level k
     const int k = min(c0 + q, N);
     const unsigned o = (unsigned)(k - 1) * lv;
     fu1[q] = LD(FU, vo + 8u, o); fu0[q] = LD(FU, vo, o); fv1[q] = LD(FV, vo + (unsigned)sj * 8u, o); fv0[q] = LD(FV, vo, o);
-    hz[q] = LD(Hz, vo, o);
-    zk[q] = LD(zw, vo, (unsigned)k * lv);
+    if constexpr (VG) {
+      zk[q] = F.Cs_w[k];   // Cs_w(k) until the column's z, h, hinv are there
+    } else {
+      hz[q] = LD(Hz, vo, o);
+      zk[q] = LD(zw, vo, (unsigned)k * lv);
+    }
   }
-  const double zw0 = zw.ld(vo, 0), zwN = zw.ld(vo, (unsigned)N * lv);
+  double zw0, zwN;
+  if constexpr (VG) {
+    const VGrid g = vg_column(d, ij);
+    zw0 = g.zw0();
+    zwN = g.zw1(N, csN);
+    double zb = g.zw(kb, csb);
+#pragma unroll
+    for (int q = 0; q < kOmR; q++) {
+      const double z = g.zw1(min(c0 + q, N), zk[q]);
+      hz[q] = q == 0 || c0 + q <= N ? z - zb : hz[q > 0 ? q - 1 : 0];
+      zk[q] = z;
+      zb = z;
+    }
+  } else {
+    zw0 = zw.ld(vo, 0);
+    zwN = zw.ld(vo, (unsigned)N * lv);
+  }
   const double wsrf = F.swflx[ij] * F.dm_r[ij] * F.dn_r[ij];
   const double CX0 = dtau * F.pm[ij] * F.pn[ij];
   const int pidx = d.p.npip > 0 ? F.pipe_idx[ij] : 0;
@@ -665,6 +722,8 @@ static size_t omega_hb_lds_bytes(unsigned nthr) { return (size_t)kOmR * nthr * s
 void setup_omega_seg() {
   (void)hipFuncSetAttribute((const void*)k_omega_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)omega_hb_lds_bytes(kOmBlock));
+  (void)hipFuncSetAttribute((const void*)k_omega_seg<true, kOmCW, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)omega_hb_lds_bytes(kOmBlock));
 }
 
 // k_omega_seg<kHB, CW> by ROMS_GPU_OMEGA_CW
@@ -673,7 +732,8 @@ static void omega_seg_cw(const Dev& d, hipStream_t s, const Range& r, double dta
   const Bounds& b = d.b;
   const dim3 gs((r.i1 - tile_i0(r.i0) + CW) / CW, r.j1 - r.j0 + 1), bs(kCX, seg_waves<CW>(b.N));
   const size_t lds = kHB ? omega_hb_lds_bytes(bs.x * bs.y) : 0;
-  hipLaunchKernelGGL((k_omega_seg<kHB, CW>), gs, bs, lds, s, d, r, dtau, hcff);
+  if (d.p.vg & (kVg2Omega << kVg2Shift)) hipLaunchKernelGGL((k_omega_seg<kHB, CW, true>), gs, bs, lds, s, d, r, dtau, hcff);
+  else hipLaunchKernelGGL((k_omega_seg<kHB, CW, false>), gs, bs, lds, s, d, r, dtau, hcff);
 }
 template <bool kHB>
 static void omega_seg(const Dev& d, hipStream_t s, const Range& r, double dtau, double hcff) {

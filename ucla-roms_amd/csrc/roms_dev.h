@@ -87,7 +87,10 @@ struct Params {
   // kernel-argument offset (without it lmd_vmix measured 2-3% slower at C3,
   // its kernels differing in nothing but their scalar-load offsets:
   // profiles/r9_retire_variants_ab.txt)
-  int reserved_[8];
+  // vgrid2 took the first of the eight: further VGrid kernels (ROMS_GPU_VGRID2 bits, 0: the streaming forms):
+  // 1 k_omega_seg, 2 k_set_huv1_chain, 4 k_uv2_fused, 8 k_visc3d_stg, 16 k_t3dmix_stg.  In force as bits 8.. of vg.
+  int vgrid2;
+  int reserved_[7];
   // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
@@ -102,12 +105,15 @@ struct Params {
   short kpp_fckeep; // levels FC(0:keep) of k_kpp_ext's LDS slot, 1..kKppFcKeepMax (ROMS_GPU_KPP_FCKEEP); above them the FC sweep is repeated
   short vgrid;      // kernels that form Hz, z_r, z_w of a column from z_sd, h, hinv (VGrid) instead of streaming the arrays, bitwise
                     // (ROMS_GPU_VGRID bits, default 11, 0: the streaming forms): 1 k_rho_eos_split, 2 k_kpp_ext, 4 k_kpp_int, 8 k_set_huv
-  short vg;         // the bits of vgrid in force: vgrid while the stored arrays are set_depth's own (the shim's validity flag), else 0
+  short vg;         // the bits of vgrid, and of vgrid2 << kVg2Shift, in force: both while the stored arrays are set_depth's own (the shim's validity flag), else 0
   double ubind;   // OBC binding velocity
   double dt, dtfast, g, rho0, vonKar, qp2, gamma2, hc;
   double rdrg, Zob, Tcoef, T0, Scoef, S0;
   double Akv_bak, Akt_bak[2];  // scalars.F:83
 };
+// the kernel-argument offsets the kernels were measured with (reserved_ above)
+static_assert(offsetof(Params, s2d_k) == 196 && offsetof(Params, ubind) == 240 && sizeof(Params) == 384,
+              "Params: no member from s2d_k on may move");
 
 // Device pointers of the model state (the "module arrays") plus scratch.
 struct Fields {
@@ -223,6 +229,9 @@ __device__ __forceinline__ int iclamp(int x, int lo, int hi) { return x < lo ? l
 // the same expressions in the same order (-ffp-contract=off), so the same bits.
 constexpr int kVgRho = 1, kVgKppExt = 2, kVgKppInt = 4, kVgHuv = 8, kVgAll = 15;   // Params::vgrid bits
 constexpr int kVgDefault = kVgRho | kVgKppExt | kVgHuv;   // k_kpp_int measured slower with it (profiles/r8_vgrid_ab.txt)
+// Params::vgrid2 bits; in Params::vg they stand kVg2Shift higher
+constexpr int kVg2Omega = 1, kVg2Huv1 = 2, kVg2Uv2 = 4, kVg2Visc = 8, kVg2T3dmix = 16, kVg2All = 31, kVg2Shift = 8;
+constexpr int kVg2Default = kVg2All;  // profiles/r10_vgrid_rest_ab.txt
 struct VGrid {
   const double *Cs_w, *Cs_r;
   double z, h, hinv, hc, ds;

@@ -150,7 +150,7 @@ void drop_graphs() {   // captured graphs hold the old Params / pointers
 }
 void vg_set(bool valid) {
   g.vgrid_valid = valid;
-  g.d.p.vg = valid ? g.d.p.vgrid : (short)0;
+  g.d.p.vg = valid ? (short)(g.d.p.vgrid | (g.d.p.vgrid2 << kVg2Shift)) : (short)0;
 }
 // the host wrote field `id`: Hz, z_r, z_w, h, hinv or a Cs table ends VGrid's validity
 void vg_host_write(int id) {
@@ -953,6 +953,9 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   // bits in roms_dev.h); ROMS_GPU_VGRID=0 for the streaming forms, 1..15 a
   // set of kernels.  Default 11: k_kpp_int (bit 4) is slower with it
   P.vgrid = (short)env_int("ROMS_GPU_VGRID", kVgDefault, 0, kVgAll);
+  // the same for omega, set_HUV1 and step3d_uv2's column kernels (the bits in
+  // roms_dev.h); ROMS_GPU_VGRID2=0 for the streaming forms
+  P.vgrid2 = env_int("ROMS_GPU_VGRID2", kVg2Default, 0, kVg2All);
   P.vg = 0;
   g.vgrid_valid = false;
   P.hoist = !env_off("ROMS_GPU_HOIST");
@@ -1243,6 +1246,11 @@ int roms_gpu_column_path(void) {
 int roms_gpu_vgrid(void) {
   REQUIRE_INIT_NOJOIN();
   return g.d.p.vgrid + (g.vgrid_valid ? 256 : 0);
+}
+
+int roms_gpu_vgrid2(void) {
+  REQUIRE_INIT_NOJOIN();
+  return g.d.p.vgrid2 + (g.vgrid_valid ? 256 : 0);
 }
 
 int roms_gpu_vgrid_check(long out[3]) {

@@ -561,6 +561,13 @@ class Model:
         self._chk(min(r, 0), "vgrid")
         return r % 256, bool(r // 256)
 
+    def vgrid2(self):
+        """(mask, valid): the same for the column kernels of omega, set_HUV1
+        and step3d_uv2 (ROMS_GPU_VGRID2, as read at init; roms_gpu_vgrid2)."""
+        r = self.L.roms_gpu_vgrid2()
+        self._chk(min(r, 0), "vgrid2")
+        return r % 256, bool(r // 256)
+
     def vgrid_mismatch(self):
         """(z_w, z_r, Hz): stored values that differ bitwise from the ones
         formed from the kept free surface, h and hinv, over set_depth's range
