@@ -10,10 +10,6 @@
   and history files (test_gpu_io.py) and the pipe/river/tide inputs
   (test_gpu_pipes.py, test_gpu_rivers.py, test_gpu_forcing.py) run on the
   padded layout by default.
-* j-marching per-level horizontal kernels (ROMS_GPU_HJC): windows in an LDS
-  ring, same expressions as the 64 x 4 tiles.
-* routines without a data dependence on two streams inside the step
-  (ROMS_GPU_PAR=1, opt-in): the same kernels on the same inputs.
 """
 import numpy as np
 import pytest
@@ -92,28 +88,3 @@ def test_device_row_pitch_decomposed_bitwise(monkeypatch):
         for f in a[r][4]:
             assert np.array_equal(a[r][4][f], b[r][4][f]), (r, f)
 
-
-@pytest.mark.parametrize("kind", ["filament_61", "basin_60", "obc_island", "c3_n100"])
-def test_j_marching_horizontal_kernels_bitwise(kind, monkeypatch):
-    """The per-level horizontal kernels that walk 64-wide strips through
-    ROMS_GPU_HJC rows with their windows in an LDS ring (default 32) equal the
-    64 x 4 tile forms (ROMS_GPU_HJC=0) bitwise; 8 rows (two ring turns per
-    block) and the default on grids whose row count is not a multiple of the
-    chunk."""
-    a = _run(kind, {"ROMS_GPU_HJC": "0"}, monkeypatch)
-    for jc in ("8", "32"):
-        b = _run(kind, {"ROMS_GPU_HJC": jc}, monkeypatch)
-        for n in FIELDS:
-            assert np.array_equal(a[n], b[n]), (jc, n)
-
-
-@pytest.mark.parametrize("kind", ["filament_61", "basin_60", "obc_island", "c3_n100"])
-def test_two_stream_step_bitwise(kind, monkeypatch):
-    """Whole steps with the independent routines on two streams (lmd_vmix
-    beside prsgrd, the corrector's omega beside rho_eos, ...; opt-in,
-    ROMS_GPU_PAR=1, measured slower) equal the one-stream order (the default)
-    bitwise, eager first step and graph replays alike."""
-    a = _run(kind, {}, monkeypatch, nsteps=5)
-    b = _run(kind, {"ROMS_GPU_PAR": "1"}, monkeypatch, nsteps=5)
-    for n in FIELDS:
-        assert np.array_equal(a[n], b[n]), n

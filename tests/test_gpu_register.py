@@ -88,9 +88,7 @@ def _ptide(o, amp=0.3):
     return amp * np.sin(2 * np.pi * x / Lx) * np.cos(np.pi * y / Ly)
 
 
-@pytest.mark.parametrize("fused", ["0", "1"])
-def test_pot_tides_prsgrd_parity(fused, monkeypatch):
-    monkeypatch.setenv("ROMS_GPU_PRSGRD_FUSED", fused)
+def test_pot_tides_prsgrd_parity():
     c = basin_cfg(nonlin=True)
     c.pot_tides = 1
     o = oracle.Oracle(c)

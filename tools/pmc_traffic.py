@@ -28,7 +28,7 @@ ROUTINE_OF = {
     # round-2 kernels: register / segment / chained forms
     "k_uv1_seg": "step3d_uv1", "k_pre_tracer_v_reg": "pre_step3d",
     "k_pre_tracer_seg": "pre_step3d", "k_pre_uv_seg": "pre_step3d", "k_uv2_fused": "step3d_uv2",
-    "k_set_huv1_chain": "set_HUV1", "k_kpp_ext": "lmd_vmix", "k_kpp_int": "lmd_vmix", "k_prsgrd_fused": "prsgrd",
+    "k_set_huv1_chain": "set_HUV1", "k_kpp_ext": "lmd_vmix", "k_kpp_int": "lmd_vmix",
     "k_bulk_flux": "bulk_flux", "k_t3dbc_edges": "step3d_t", "k_t3dbc_corners": "step3d_t", "k_u3dbc": "step3d_uv2",
     "k_v3dbc": "step3d_uv2", "k_pre_tracer_h1": "pre_step3d", "k_step3d_t_h1": "step3d_t",
     # round-3 late: staged-window forms

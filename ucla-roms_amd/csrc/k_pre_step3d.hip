@@ -163,154 +163,6 @@ __global__ void __launch_bounds__(kBX * kBY) k_pre_tracer_h1(Dev d, Range R, Pre
   }
 }
 
-// ---- j-marching form of k_pre_tracer_h1 (Params::h_jc): a block of 64 x 4
-// threads walks a 64-wide strip through jc rows of one level, 4 rows per
-// step.  The windows (masks, FlxU/FlxV, each tracer) live in an 8-row LDS ring
-// (AccTR): each step brings in only the 4 rows the next tile needs beyond the
-// ones already there, loaded into registers while the current tile computes
-// (with the next tile's lane inputs), so every window row is read from HBM
-// once per strip instead of twice (the 64 x 4 tiles' 4-row j-halo: 8 window
-// rows per 4 tile rows).  Same expressions, same order: bit-identical. ----
-template <int NTT>
-struct TracerRing {
-  double UM[kRingH * kUVW], VM[kRingH * kUVW], FU[kRingH * kUVW], FV[kRingH * kUVW], T[NTT][kRingH * kUVW];
-};
-// window rows [r0, r0 + nr) of the ring fields: entry q of the row block is
-// register m of thread tid (q = tid + m*256)
-template <int NTT, int NR>
-struct TracerRows {
-  double um[NR], vm[NR], fu[NR], fv[NR], t[NTT][NR];
-  __device__ __forceinline__ void load(const Bounds& b, const Fields& F, int tid, int ib, int r0, int nr, long kk,
-                                       long tlev) {
-#pragma unroll
-    for (int m = 0; m < NR; m++) {
-      const int q = tid + m * kBX * kBY;
-      const int i = ib + q % kUVW, j = r0 + q / kUVW;
-      const bool ok = q < nr * kUVW && i >= -1 && i <= b.Lm + 2 && j >= -1 && j <= b.Mm + 2;
-      const long o = ok ? IJ(b, i, j) : 0;
-      um[m] = ok ? F.umask[o] : 0.0;
-      vm[m] = ok ? F.vmask[o] : 0.0;
-      fu[m] = ok ? F.FlxU[o + kk] : 0.0;
-      fv[m] = ok ? F.FlxV[o + kk] : 0.0;
-#pragma unroll
-      for (int t = 0; t < NTT; t++) this->t[t][m] = ok ? F.t[tlev + (long)t * 3 * b.n3 + o + kk] : 0.0;
-    }
-  }
-  __device__ __forceinline__ void store(TracerRing<NTT>& W, int tid, int r0, int nr, int jb) const {
-#pragma unroll
-    for (int m = 0; m < NR; m++) {
-      const int q = tid + m * kBX * kBY;
-      if (q < nr * kUVW) {
-        const int s = (q % kUVW) + ((r0 + q / kUVW - jb) & (kRingH - 1)) * kUVW;
-        W.UM[s] = um[m]; W.VM[s] = vm[m]; W.FU[s] = fu[m]; W.FV[s] = fv[m];
-#pragma unroll
-        for (int t = 0; t < NTT; t++) W.T[t][s] = this->t[t][m];
-      }
-    }
-  }
-};
-template <int NTT, bool kHB>
-__global__ void __launch_bounds__(kBX * kBY) k_pre_tracer_hj(Dev d, Range R, PreCoef c, int nstp, int nnew, int nrhs,
-                                                           int jc) {
-  const uint3 bI = xcd_tile();
-  __shared__ TracerRing<NTT> W;
-  const Bounds& b = d.b;
-  const Fields& F = d.f;
-  const int k = 1 + (int)bI.z, indx = 3 - nstp;
-  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, jc0 = R.j0 + (int)bI.y * jc;
-  const int jend = min(jc0 + jc - 1, R.j1);
-  const int ib = i0 - 2, jb = jc0 - 2;
-  const long kk = (long)(k - 1) * b.n2, n2 = b.n2, tlev = (long)(nrhs - 1) * b.n3;
-  const int tid = threadIdx.x + kBX * threadIdx.y;
-  constexpr int NT = kBX * kBY;
-  constexpr int NR0 = (kRingH * kUVW + NT - 1) / NT, NR4 = (kBY * kUVW + NT - 1) / NT;
-  // the lane's own inputs of tile row j (hz_bak_fwd's, pre_step3d4S.F:136-148, and the time levels)
-  struct Lane {
-    double fu0, fu1, fv0, fv1, we1, wi1, we0, wi0, hbo, pm, pn, hzo, ts[NTT], ti[NTT];
-  };
-  const int i = i0 + (int)threadIdx.x;
-  auto load_lane = [&](Lane& L, int j) {
-    const bool act = i >= R.i0 && i <= R.i1 && j <= jend;
-    const bool formed = kHB && act && i >= b.istr && j >= b.jstr;
-    const long ij = act ? IJ(b, i, j) : IJ(b, R.i0, R.j0), o = ij + kk, w = ij + (long)k * n2;
-    L.fu0 = L.fu1 = L.fv0 = L.fv1 = L.we1 = L.wi1 = L.we0 = L.wi0 = L.hbo = 0.0;
-    if (formed) {
-      L.hbo = F.c3[o];
-    } else {
-      L.fu0 = F.FlxU[o]; L.fu1 = F.FlxU[o + 1]; L.fv0 = F.FlxV[o]; L.fv1 = F.FlxV[o + b.nx2];
-      L.we1 = F.We[w]; L.wi1 = F.Wi[w]; L.we0 = F.We[w - n2]; L.wi0 = F.Wi[w - n2];
-    }
-    L.pm = F.pm[ij]; L.pn = F.pn[ij]; L.hzo = F.Hz[o];
-#pragma unroll
-    for (int t = 0; t < NTT; t++) {
-      const long tb = (long)t * 3 * b.n3;
-      L.ts[t] = F.t[(long)(nstp - 1) * b.n3 + tb + o];
-      L.ti[t] = F.t[(long)(indx - 1) * b.n3 + tb + o];
-    }
-  };
-  // prologue: the first tile's window (8 rows) and lane inputs
-  Lane L;
-  {
-    TracerRows<NTT, NR0> X;
-    X.load(b, F, tid, ib, jb, kRingH, kk, tlev);
-    load_lane(L, jc0 + (int)threadIdx.y);
-    X.store(W, tid, jb, kRingH, jb);
-  }
-  __syncthreads();
-  const AccTR a0{nullptr, W.UM, W.VM, W.FU, W.FV, ib, jb};
-  for (int j0 = jc0; j0 <= jend; j0 += kBY) {
-    const bool more = j0 + kBY <= jend;
-    TracerRows<NTT, NR4> X;
-    Lane Ln;
-    if (more) {   // the next tile's 4 new window rows and lane inputs, in flight during this tile
-      X.load(b, F, tid, ib, j0 + kBY + 2, kBY, kk, tlev);
-      load_lane(Ln, j0 + kBY + (int)threadIdx.y);
-    }
-    const int j = j0 + (int)threadIdx.y;
-    const bool act = i >= R.i0 && i <= R.i1 && j <= jend;
-    const bool in = act && i >= b.istr && j >= b.jstr;
-    if (act) {
-      const long ij = IJ(b, i, j), o = ij + kk;
-      double hb;
-      if (kHB && in) {
-        hb = L.hbo;
-      } else {
-        const double cff = 0.5 * c.dtau;
-        const double FlxDiv = cff * L.pm * L.pn * (L.fu1 - L.fu0 + L.fv1 - L.fv0 + L.we1 + L.wi1 - L.we0 - L.wi0);
-        hb = L.hzo + FlxDiv;
-        const double hf = L.hzo - FlxDiv;
-        F.c2[o] = hf;  // Hz_fwd, Hz_bak kept for the column solves (range istr-1.., jstr-1..)
-        F.c3[o] = hb;
-      }
-      if (in) {
-        const double hz = L.hzo;
-#pragma unroll
-        for (int t = 0; t < NTT; t++) {
-          const int itrc = t + 1;
-          AccTR a = a0;
-          a.T = W.T[t];
-          double FX0 = tracer_fx(b, a, i, j, false), FX1 = tracer_fx(b, a, i + 1, j, false);
-          double FE0 = tracer_fe(b, a, i, j, false), FE1 = tracer_fe(b, a, i, j + 1, false);
-          if (d.p.nriv > 0) {   // river inflow faces (compute_horiz_tracer_fluxes.h:217-246)
-            river_tracer_flux(d, 0, i, j, k, itrc, FX0); river_tracer_flux(d, 0, i + 1, j, k, itrc, FX1);
-            river_tracer_flux(d, 1, i, j, k, itrc, FE0); river_tracer_flux(d, 1, i, j + 1, k, itrc, FE1);
-          }
-          const long tb = (long)t * 3 * b.n3;
-          const double tsk = L.ts[t];
-          F.t[(long)(nnew - 1) * b.n3 + tb + o] =
-              hb * (c.cf_stp * tsk + c.cf_bak * L.ti[t]) - c.dtau * L.pm * L.pn * (FX1 - FX0 + FE1 - FE0);
-          F.t[(long)(indx - 1) * b.n3 + tb + o] = hz * tsk;
-        }
-      }
-    }
-    if (!more) break;
-    __syncthreads();   // this tile's reads of the 4 oldest rows are done
-    X.store(W, tid, j0 + kBY + 2, kBY, jb);
-    L = Ln;
-    __syncthreads();
-  }
-}
-
 // ---- tracers, vertical part per column: spline advection on t(nrhs), then
 // implicit diffusion with Wi up-winding on Hz_fwd (LDS slots A, B). ----
 template <class C>
@@ -1094,7 +946,7 @@ double pre_step3d_dtau(const Dev& d, const Tlev& t) {
   return t.iic == t.forw_start ? 0.5 * d.p.dt : d.p.dt * (1.0 - AM3_crv);
 }
 
-void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool hb_done, const Side* side) {
+void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool hb_done) {
   const Bounds& b = d.b;
   PreCoef c;
   const double AM3_crv = 1.0 / 6.0;
@@ -1109,18 +961,7 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   // the rows strips cover (k_tracer_strip.hip), the rest on tiles
   auto horiz_tiles = [&](const Range& rh) {
     const dim3 gh = grid3_of(rh, b.N), bh(kBX, kBY);
-    if (d.p.hoist && d.p.h_jc > 0 && (b.NT == 1 || b.NT == 2)) {
-      const dim3 g = grid3_jc(rh, b.N, d.p.h_jc);
-      const int jc = d.p.h_jc;
-      if (b.NT == 2 && hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_hj<2, true>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
-      else if (b.NT == 2)
-        hipLaunchKernelGGL((k_pre_tracer_hj<2, false>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
-      else if (hb_done)
-        hipLaunchKernelGGL((k_pre_tracer_hj<1, true>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
-      else
-        hipLaunchKernelGGL((k_pre_tracer_hj<1, false>), g, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs, jc);
-    } else if (d.p.hoist && b.NT == 2 && hb_done)
+    if (d.p.hoist && b.NT == 2 && hb_done)
       hipLaunchKernelGGL((k_pre_tracer_h1<2, true>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
     else if (d.p.hoist && b.NT == 2)
       hipLaunchKernelGGL((k_pre_tracer_h1<2, false>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
@@ -1133,7 +974,7 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   };
   {
     int jA = 0, jB = -1;
-    if (d.p.hoist && d.p.h_jc == 0 &&
+    if (d.p.hoist &&
         launch_tracer_strip(d, s, RH, 1, false, hb_done, t.nnew, t.nrhs, c.dtau, c.cf_stp, c.cf_bak, t.nstp, jA, jB)) {
       if (jA > RH.j0) horiz_tiles(Range{RH.i0, RH.i1, RH.j0, jA - 1});
       if (jB < RH.j1) horiz_tiles(Range{RH.i0, RH.i1, jB + 1, RH.j1});
@@ -1141,32 +982,20 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
       horiz_tiles(RH);
     }
   }
-  // The tracer column solves (t(nnew), reading Hz_fwd) and the momentum ones
-  // (u, v(nnew), u, v(indx), reading Hz_fwd/bak, ru, rv) share no output:
-  // with a side stream they run side by side once the horizontal tracer
-  // kernel has formed the ring of Hz_fwd/bak both read
-  hipStream_t st = s;
-  if (side) {
-    (void)hipEventRecord(side->efork, s);
-    (void)hipStreamWaitEvent(side->s2, side->efork, 0);
-    st = side->s2;
-  }
   dim3 gt = gridc_of(RI);
   gt.z = b.NT;
   if (d.p.colseg && d.p.seg_buf)
-    hipLaunchKernelGGL(k_pre_tracer_segb, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, RI, c, t.nnew,
+    hipLaunchKernelGGL(k_pre_tracer_segb, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, RI, c, t.nnew,
                        t.nrhs);
   else if (d.p.colseg)
-    hipLaunchKernelGGL(k_pre_tracer_seg, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, st, d, RI, c, t.nnew,
+    hipLaunchKernelGGL(k_pre_tracer_seg, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, RI, c, t.nnew,
                        t.nrhs);
   else if ((d.p.colreg & 2) && b.N == 50 && !d.f.colscr)
-    hipLaunchKernelGGL(k_pre_tracer_v_reg<50>, gt, dim3(kCX), col_lds_bytes(1, 50), st, d, RI, c, t.nnew, t.nrhs);
+    hipLaunchKernelGGL(k_pre_tracer_v_reg<50>, gt, dim3(kCX), col_lds_bytes(1, 50), s, d, RI, c, t.nnew, t.nrhs);
   else if (d.f.colscr)
-    hipLaunchKernelGGL(k_pre_tracer_v<ColGlb>, gt, dim3(kCX), 0, st, d, RI, c, t.nnew, t.nrhs);
+    hipLaunchKernelGGL(k_pre_tracer_v<ColGlb>, gt, dim3(kCX), 0, s, d, RI, c, t.nnew, t.nrhs);
   else
-    hipLaunchKernelGGL(k_pre_tracer_v<ColLds>, gt, dim3(kCX), col_lds_bytes(2, b.N), st, d, RI, c, t.nnew, t.nrhs);
-  for (int itrc = 1; itrc <= b.NT && side; itrc++) launch_t3dbc(d, st, t, itrc);
-  if (side) launch_exchange_tracers(d, st, t.nnew);
+    hipLaunchKernelGGL(k_pre_tracer_v<ColLds>, gt, dim3(kCX), col_lds_bytes(2, b.N), s, d, RI, c, t.nnew, t.nrhs);
   if (!uv_done) launch_uv_horiz(d, s, t.nrhs, 0);
   Range Rd{b.istrU - 1, b.iend, b.jstrV - 1, b.jend};
   hipLaunchKernelGGL(k_rd, grid_of(Rd), dim3(kBX, kBY), 0, s, d, Rd, t.nstp);
@@ -1193,11 +1022,6 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   launch_river_uv(d, s, t.nnew, 1);   // pre_step3d4S.F:493-522
   launch_u3dbc(d, s, t);
   launch_v3dbc(d, s, t);
-  if (side) {
-    (void)hipEventRecord(side->ejoin, st);
-    (void)hipStreamWaitEvent(s, side->ejoin, 0);
-    return;
-  }
   for (int itrc = 1; itrc <= b.NT; itrc++) launch_t3dbc(d, s, t, itrc);
   launch_exchange_tracers(d, s, t.nnew);
 }

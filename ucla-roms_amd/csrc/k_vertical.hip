@@ -1073,7 +1073,7 @@ __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Ran
 // (r3_zl_p_in_rho_ab.txt: C2 +0.08 ms/step, C3 -2.2 ms/step)
 bool p_in_rho(const Dev& d) {
   const Bounds& b = d.b;
-  return d.p.p_in_rho && d.p.nonlin_eos && d.p.prs_split && !d.p.tides && b.N >= 2 && b.istrE <= 0 &&
+  return d.p.p_in_rho && d.p.nonlin_eos && !d.p.tides && b.N >= 2 && b.istrE <= 0 &&
          b.iendE >= b.Lm && b.jstrE <= 0 && b.jendE >= b.Mm;
 }
 void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx) {

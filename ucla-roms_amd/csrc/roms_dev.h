@@ -55,7 +55,11 @@ struct Params {
   int tides;                                // TIDES pot_tides: ptide in prsgrd
   int bulk_frc;                             // BULK_FRC (k_bulk.hip; u* from sustr_r/svstr_r in lmd_kpp)
   // ---- kernel selection: the form of a routine, never its result ----
-  int prs_split;  // 1: two-kernel prsgrd (default), 0: k_prsgrd_fused (ROMS_GPU_PRSGRD_FUSED=1)
+  // (the two unnamed ints stand where a retired switch stood, so that no member
+  // moves: with them gone and reserved_ grown instead, seg_order .. seg_buf 4-8 B
+  // lower, the C3 step, set_HUV and step3d_uv2 measured above the parent,
+  // profiles/r11_retire_three_ab.txt)
+  int : 32;
   int s2d_split;  // 1: step2d as separate zeta / momentum kernels (ROMS_GPU_S2D_SPLIT=1)
   int colseg;     // 1: segment-partitioned column solvers (k_colseg.h; N > 63, ROMS_GPU_COLSEG=0/1)
   int colreg;     // bit 2: register-resident k_pre_tracer_v_reg where compiled for N (ROMS_GPU_COLREG=0: the LDS form)
@@ -67,7 +71,7 @@ struct Params {
   int hoist;        // per-level horizontal kernels with every global load at entry (ROMS_GPU_HOIST=0: per-phase forms)
   int chain_dirz;   // chain kernels (set_HUV1, uv2): one direction per block (ROMS_GPU_CHAIN_DIRZ=0: both in turn)
   int prs_fuse_uv;  // whole steps: horizontal momentum r.h.s. inside prsgrd (ROMS_GPU_PRS_UV=0: separate)
-  int h_jc;       // rows per block of the j-marching horizontal kernels (multiple of 4; ROMS_GPU_HJC, 0: 64 x 4 tiles)
+  int : 32;
   int prs_buf;    // k_prsgrd_uv windows through buffer loads (ROMS_GPU_PRS_BUF)
   int prs_strip;  // prsgrd + momentum r.h.s. in j-marching strips (k_prsgrd_strip; ROMS_GPU_PRS_STRIP=0: tiles)
   int t_strip;    // horizontal tracer advection in j-marching strips (k_tracer_strip; ROMS_GPU_T_STRIP=0: tiles)
@@ -82,7 +86,7 @@ struct Params {
   int preuv_lds;  // k_pre_uv_seg: u(indx) stored and u(nstp)/u(indx) combined in the spline phase (ROMS_GPU_PREUV_LDS=0: reloads)
   int seg_jrows;  // rows j per block of the momentum segment solvers (1..kSegJMax; ROMS_GPU_SEG_JROWS)
   int seg_buf;    // 1: segment solvers with buffer loads (k_*_segb; ROMS_GPU_SEG_BUF=0: the pointer forms)
-  // eight retired switches stood among the ints above: their room stays, so
+  // eight more retired switches stood among the ints above: their room stays, so
   // that every member from here on -- and Fields after Params -- keeps its
   // kernel-argument offset (without it lmd_vmix measured 2-3% slower at C3,
   // its kernels differing in nothing but their scalar-load offsets:
@@ -499,21 +503,10 @@ void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up = -1, b
 // j-marching strips (mode 0 step3d_t, 1 pre_step3d); false: not covered
 bool launch_tracer_strip(const Dev& d, hipStream_t s, const Range& R, int mode, bool up, bool hb_done, int nnew,
                          int nrhs, double dtau, double cf_stp, double cf_bak, int nstp, int& jA, int& jB);
-bool p_in_rho(const Dev& d);
-void launch_prsgrd_P(const Dev& d, hipStream_t s);   // prsgrd's P alone (k_prsgrd_P)   // every rho_eos also forms prsgrd's P (k_vertical.hip)
+bool p_in_rho(const Dev& d);   // every rho_eos also forms prsgrd's P (k_vertical.hip)
 bool prsgrd_can_fuse_uv(const Dev& d);
-// A second stream for work with no data dependence on the main stream's
-// (enqueue_step, single rank): the callee forks `s2` off `s` with `efork`
-// and joins it back with `ejoin` before returning.
-struct Side {
-  hipStream_t s2;
-  hipEvent_t efork, ejoin;
-};
 // hb_done: the interior cells' Hz_bak/Hz_fwd are in c3/c2 already (launch_omega)
-// side: the tracer solves (and their boundary conditions and exchange) run on
-// side->s2 beside the momentum ones
-void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false, bool hb_done = false,
-                       const Side* side = nullptr);
+void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false, bool hb_done = false);
 void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false);
 void launch_visc3d(const Dev& d, hipStream_t s, const Tlev& t);
 void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1, const double* w2);

@@ -99,12 +99,7 @@ struct Ctx {
   Bounds hb{};               // the host layout's Bounds (nx2 = Lm+4)
   double* stage = nullptr;
   long stage_n = 0;
-  // Routines with no data dependence between them run on two streams inside
-  // the step (single rank; opt-in, ROMS_GPU_PAR=1): see enqueue_step
-  int par = 0;               // two-stream pair mask (enqueue_step)
   long step_exch = 0;        // halo exchanges in the last enqueued step (roms_gpu_halo_exchanges)
-  hipStream_t s2 = nullptr;
-  hipEvent_t pev[8] = {};
 };
 // One context per host thread: a process normally drives one GPU/subdomain
 // from one thread; tests drive several subdomains from threads of one process.
@@ -407,9 +402,6 @@ void free_all() {
   if (g.h_diag) { (void)hipHostFree(g.h_diag); g.h_diag = nullptr; }
   if (g.d_diag) { (void)hipFree(g.d_diag); g.d_diag = nullptr; }
   if (g.s) { (void)hipStreamDestroy(g.s); g.s = nullptr; }
-  if (g.s2) { (void)hipStreamDestroy(g.s2); g.s2 = nullptr; }
-  for (hipEvent_t& e : g.pev)
-    if (e) { (void)hipEventDestroy(e); e = nullptr; }
   g.inited = false;
 }
 
@@ -476,30 +468,6 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   (void)s2d_edge_modes_taken(true);   // the modes of this step's fast steps (roms_gpu_horizontal_path)
   const bool pot = g.cfg.pot_tides != 0;
   g.rho_slot = 0;
-  // Two streams where the reference's order has no data dependence (single
-  // rank -- a multi-rank halo exchange keeps one order on its transport --
-  // and not while one routine is being timed):
-  //   predictor: lmd_vmix(nstp) (writes Akv, Akt, hbls, hbbl, ghat and its
-  //     own work arrays) beside prsgrd (writes ru, rv); pre_step3d reads both
-  //   corrector: omega (We, Wi) beside rho_eos (rho1, qp1, P, bvf, rhoA,
-  //     rhoS), then lmd_vmix(nrhs) beside prsgrd; step3d_uv1 reads all
-  // Same kernels, same inputs: the results are bitwise those of one stream.
-  // The low-occupancy column kernels (KPP, omega) fill CUs the other
-  // routine leaves idle.
-  // g.par: a mask of the pairs (ROMS_GPU_PAR=1: all; ROMS_GPU_PAR_MASK=bits):
-  // 1 predictor lmd_vmix | prsgrd, 2 corrector omega | rho_eos, 4 corrector
-  // lmd_vmix | prsgrd, 8 pre_step3d tracer | momentum solves, 16 predictor P
-  // (linear EOS) | set_HUV, omega
-  const int pm = d.halo == nullptr && g.timed < 0 ? g.par : 0;
-  hipStream_t s2 = g.s2;
-  auto fork = [&](int k) {   // s2 continues after everything queued on s so far
-    (void)hipEventRecord(g.pev[k], s);
-    (void)hipStreamWaitEvent(s2, g.pev[k], 0);
-  };
-  auto join = [&](int k) {   // s continues after everything queued on s2 so far
-    (void)hipEventRecord(g.pev[k], s2);
-    (void)hipStreamWaitEvent(s, g.pev[k], 0);
-  };
   // Multi-rank runs (Halo::xoverlap: the default with > 1 rank when every
   // rank drives its own GPU; not while one routine is timed): the trailing exchange of a producer in DEFER(...) runs
   // on the halo stream beside the routines that follow it, and XJOIN(t) makes
@@ -534,22 +502,14 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   frc_step_phase(d, s, 1, pot);     // set_bry_all '1/2 fwd' + set_tides (main.F:389-394)
   if (!rho_current) TIMED(ROMS_R_RHO_EOS, launch_rho_eos(d, s, T, T.nrhs));
   // every rho_eos of the library leaves P current (p_in_rho): the
-  // step-opening one, or the previous step's closing one it reuses; else
-  // (linear EOS) prsgrd's P integral (rho, z_r, z_w: nothing set_HUV or
-  // omega writes) runs on the side stream beside them
+  // step-opening one, or the previous step's closing one it reuses
   const bool p_ready = p_in_rho(d);
-  const bool p_side = (pm & 16) && !p_ready && d.p.prs_split;
-  if (p_side) {
-    fork(7);
-    launch_prsgrd_P(d, s2);
-  }
   TIMED(ROMS_R_SET_HUV, DEFER(launch_set_huv(d, s, T, store_huv)));   // FlxU, FlxV
   const long x_huv = xt;
-  const bool lmd2 = g.cfg.lmd_mixing && (pm & 1);
   // lmd_vmix(nstp) reads u, v(nstp), bvf, Hz, z_r, z_w and the surface fluxes:
   // none of set_HUV's or omega's outputs, so on a multi-rank run it goes first
   // and covers set_HUV's exchange (Akv, Akt, hbls, hbbl follow on the halo stream)
-  const bool lmd_early = xo && g.cfg.lmd_mixing && !lmd2;
+  const bool lmd_early = xo && g.cfg.lmd_mixing;
   if (lmd_early) TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nstp)));
   XJOIN_T(1, x_huv);   // omega reads FlxU(iend+1), FlxV(jend+1)
   // the predictor's omega also forms pre_step3d's Hz_bak/Hz_fwd (nothing in
@@ -557,24 +517,15 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   bool hb_done = false;
   TIMED(ROMS_R_OMEGA, DEFER(hb_done = launch_omega(d, s, T, d.p.omega_hb && d.p.hoist && T.nrhs != 3 ?
                                                                  0.5 * pre_step3d_dtau(d, T) : 0.0)));
-  if (p_side) join(7);
-  if (lmd2) {
-    fork(0);
-    launch_lmd_vmix(d, s2, T, T.nstp);
-  } else if (g.cfg.lmd_mixing && !lmd_early) {
-    TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp));
-  }
+  if (g.cfg.lmd_mixing && !lmd_early) TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp));
   // the horizontal momentum r.h.s. of pre_step3d / step3d_uv1 rides in the
   // prsgrd kernel just before them (prsgrd_can_fuse_uv; nothing between the
   // two touches u, v(nrhs), FlxU, FlxV, Hz or ru, rv); it reads neither We, Wi
   // nor the mixing coefficients, whose exchanges it covers
   const bool fuse_uv = prsgrd_can_fuse_uv(d);
-  TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 0 : -1, p_ready || p_side));
-  if (lmd2) join(1);
+  TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 0 : -1, p_ready));
   XJOIN_T(2, xt);   // pre_step3d reads We, Akv, Akt across the halo
-  const Side side{s2, g.pev[5], g.pev[6]};
-  TIMED(ROMS_R_PRE_STEP3D,
-        DEFER(launch_pre_step3d(d, s, T, fuse_uv, hb_done, (pm & 8) ? &side : nullptr)));   // t(nnew)
+  TIMED(ROMS_R_PRE_STEP3D, DEFER(launch_pre_step3d(d, s, T, fuse_uv, hb_done)));   // t(nnew)
   const long x_pre = xt;
   // set_HUV1 reads u, v(nnew), Hz and the barotropic averages, no tracer
   TIMED(ROMS_R_SET_HUV1, DEFER(launch_set_huv1(d, s, T)));   // FlxU, FlxV, u, v(nnew)
@@ -590,26 +541,14 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
     XJOIN_T(8, x_huv1);
     TIMED(ROMS_R_OMEGA, DEFER(launch_omega(d, s, T)));   // We, Wi
   } else {
-    if (pm & 2) {
-      fork(2);
-      launch_omega(d, s2, T);
-    } else {
-      TIMED(ROMS_R_OMEGA, launch_omega(d, s, T));
-    }
+    TIMED(ROMS_R_OMEGA, launch_omega(d, s, T));
     TIMED(ROMS_R_RHO_EOS, launch_rho_eos(d, s, T, T.nrhs));
   }
   frc_step_phase(d, s, 2, pot);     // set_forces, '1/2 fwd' (main.F:433)
   launch_bulk_flux(d, s, T.nrhs);   // set_forces (main.F:433): BULK_FRC only
-  const bool lmd2c = g.cfg.lmd_mixing && (pm & 4);
-  if (lmd2c) {
-    fork(3);   // after rho_eos (bvf) and the bulk fluxes (stflx, srflx, sustr_r)
-    launch_lmd_vmix(d, s2, T, T.nrhs);
-  } else if (g.cfg.lmd_mixing) {
-    TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs)));   // Akv, Akt, hbls, hbbl
-  }
+  if (g.cfg.lmd_mixing) TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs)));   // Akv, Akt, hbls, hbbl
   frc_step_phase(d, s, 3, pot);     // set_bry_all 'forward' + set_tides (main.F:438-441)
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 1 : -1, p_ready));
-  if ((pm & 2) || lmd2c) join(4);
   XJOIN_T(16, xt);   // step3d_uv1 reads We and Akv across the halo
   TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_uv));
   if (g.cfg.uv_vis2) TIMED(ROMS_R_VISC3D, launch_visc3d(d, s, T));
@@ -863,11 +802,6 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   P.tides = cfg->pot_tides != 0;
   P.bulk_frc = cfg->bulk_frc != 0;
   P.iso = cfg->adv_isoneutral != 0;
-  // fused one-kernel prsgrd (k_prsgrd_fused): bit-identical, fewer bytes,
-  // but measured slower at C2 (0.50 vs 0.38 ms per call: a per-level walk
-  // of 2 blocks per CU hides less latency than the level-parallel grid)
-  // and only 4% faster at C3 -- opt-in, ROMS_GPU_PRSGRD_FUSED=1
-  P.prs_split = !env_on("ROMS_GPU_PRSGRD_FUSED");
   P.uv_vis2 = cfg->uv_vis2; P.ts_dif2 = cfg->ts_dif2;
   P.s2d_split = env_on("ROMS_GPU_S2D_SPLIT");
   P.dt = cfg->dt; P.dtfast = cfg->dt / (double)cfg->ndtfast; P.g = cfg->g; P.rho0 = cfg->rho0;
@@ -925,12 +859,6 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     P.omega_cw = v == 32 || v == 64 ? v : 16;
   }
   P.preuv_lds = !env_off("ROMS_GPU_PREUV_LDS");
-  // j-marching per-level horizontal kernels: rows per block (ROMS_GPU_HJC;
-  // 0 = off, the default: k_pre_tracer_hj measured slower at C3, 12.15 ->
-  // 12.65 ms per pre_step3d, r4c: the 64 x 4 tiles' j-halo rows are mostly
-  // L2 hits already (PMC 16.2 passes against 14), and the ring's in-flight
-  // rows and lanes halve the waves per SIMD)
-  P.h_jc = env_int("ROMS_GPU_HJC", 0, 0, 1 << 30) / 4 * 4;
   // visc3d with staged raw windows (bitwise): C3 2.34 -> 1.94 ms, C2 0.35 -> 0.30 ms
   // (r3_zq_visc_stg_ab.txt); ROMS_GPU_VISC_STG=0 for per-point loads
   P.visc_stg = !env_off("ROMS_GPU_VISC_STG");
@@ -993,17 +921,6 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     return -2;
   }
   CHECK_HIP(hipStreamCreateWithFlags(&g.s, hipStreamNonBlocking));
-  CHECK_HIP(hipStreamCreateWithFlags(&g.s2, hipStreamNonBlocking));
-  for (hipEvent_t& e : g.pev) CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  {
-    // measured slower than one stream (C3 60.5 -> 62.5, C2 6.40 -> 6.46 ms per
-    // step, profiles/r4_j_two_stream_ab.txt): the concurrent kernels compete
-    // for CUs and LDS (the segment solvers hold one block per CU), so the
-    // second stream is opt-in, ROMS_GPU_PAR=1
-    const char* em = getenv("ROMS_GPU_PAR_MASK");
-    g.par = env_on("ROMS_GPU_PAR") ? 31 : 0;
-    if (em) g.par = atoi(em) & 31;
-  }
   g.guard = env_on("ROMS_GPU_GUARD");
   const Bounds& b = g.d.b;
   // the 2-D fields first and next to each other (then the 2-D scratch), so
