@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 21
+#define ROMS_GPU_ABI_VERSION 22
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -347,6 +347,24 @@ int roms_gpu_kpp_lean(void);
 int roms_gpu_vgrid(void);
 int roms_gpu_vgrid2(void);
 int roms_gpu_vgrid_check(long out[3]);
+/* T and S in one block of the tracer segment solvers (ABI 22).
+ * Without LMD_DDMIX and with Akt_bak[0], Akt_bak[1] the same bits, lmd_vmix
+ * leaves Akt(isalt) bit for bit Akt(itemp), so the two tracers' vertical
+ * systems are one matrix with two right-hand sides.  The kernels of
+ * ROMS_GPU_T_PAIR (read at init; a mask, default 3, 0 for one block per
+ * tracer) then load and factorise it once for both (NT = 2, buffer segment
+ * path), every field keeping its bits:
+ *   1  k_pre_tracer_segb_pair (pre_step3d)   2  k_step3d_t_segb_pair (step3d_t)
+ * They do so only while that equality is known: every lmd_vmix (the routine,
+ * or inside a whole step) establishes it under the conditions above; writing
+ * Akt from the host (roms_gpu_copy_in, roms_gpu_upload) ends it until the next
+ * lmd_vmix, and pre_step3d or step3d_t called on its own after such a write
+ * uses the host's Akt(isalt) for S, one block per tracer.
+ * roms_gpu_tracer_pair returns mask + 256 * (equality known), negative before
+ * init; launches[0], launches[1] (if not NULL) get the pair-form launches of
+ * pre_step3d and of step3d_t this host thread enqueued since init (a replayed
+ * graph counts those of its capture).                                        */
+int roms_gpu_tracer_pair(long launches[2]);
 /* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
  * edges and the ROMS_GPU_* switches by the same host functions the launchers
  * call:

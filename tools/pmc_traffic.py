@@ -11,6 +11,7 @@ separately.  rho_eos runs twice per step (the step-opening one is reused).
 
 usage: python tools/pmc_traffic.py FETCH_counter_collection.csv WRITE_counter_collection.csv
           --steps-marker k_step3d_t_v --out profiles/pmc_traffic.json
+       (--steps-marker A,B: whichever of the kernels the run took)
 """
 import argparse
 import collections
@@ -36,6 +37,8 @@ ROUTINE_OF = {
     # round 5: buffer-addressed segment solvers
     "k_pre_tracer_segb": "pre_step3d", "k_pre_uv_segb": "pre_step3d", "k_uv1_segb": "step3d_uv1",
     "k_step3d_t_segb": "step3d_t",
+    # round 12: T and S in one block
+    "k_pre_tracer_segb_pair": "pre_step3d", "k_step3d_t_segb_pair": "step3d_t",
     # round 6: prsgrd + momentum r.h.s. in j-marching strips
     "k_prsgrd_strip": "prsgrd",
 }
@@ -71,7 +74,7 @@ def main():
     a = ap.parse_args()
     f, fc = read(a.fetch, "FETCH_SIZE")
     w, _ = read(a.write, "WRITE_SIZE")
-    steps = fc.get(a.steps_marker, 0)
+    steps = sum(fc.get(m, 0) for m in a.steps_marker.split(","))   # one of them runs once per step
     if steps == 0:
         raise SystemExit("marker kernel %s not found" % a.steps_marker)
     kern = {}

@@ -296,6 +296,135 @@ __device__ __forceinline__ void spline_fc_seg(const SegSpan& sg, int N, SegXchg&
   for (int q = 0; q < KR; q++) fc[q] = seg_live(q, ns) ? T.D[q] : xR;
 }
 
+// ---- one matrix, two right-hand sides (the T and S columns of a tracer
+// solver while both see the same Akt: k_pre_tracer_segb_pair,
+// k_step3d_t_segb_pair).  rm, C, E and
+// the coupling's al, be, all, bel, rden, Vt, Qp, gb, Vs, Qs depend on the
+// matrix alone and are formed once; D, y, yl, Ut, Pp, ga, Us, Ps exist per
+// right-hand side.  Every expression is SegTri's, on the same operands in the
+// same order, so each right-hand side's solution is bit for bit the one
+// SegTri gives it alone. ----
+struct SegXchg2 {
+  double v[8][kSegMaxS][kSegCW * kSegJMax];   // y0, al, be, yl0, all, bel, y1, yl1
+};
+template <int KR>
+struct SegTri2 {
+  double C[KR], E[KR], D0[KR], D1[KR];
+  // row(q, a, b, c, d0, d1): a x_{q-1} + b x_q + c x_{q+1} = d0 | d1
+  template <int G = kSegLoadGroup, class RowF>
+  __device__ __forceinline__ void eliminate(int n, RowF row) {
+    double Cp = 0.0, Ep = 1.0, Dp0 = 0.0, Dp1 = 0.0;
+#pragma unroll
+    for (int q = 0; q < KR; q++) {
+      double a, b, c, d0, d1;
+      row(q, a, b, c, d0, d1);
+      const double rm = seg_rcp(b - a * Cp);
+      const double Cq = c * rm, Eq = -a * Ep * rm;
+      const double Dq0 = (d0 - a * Dp0) * rm, Dq1 = (d1 - a * Dp1) * rm;
+      const bool live = seg_live(q, n);
+      C[q] = live ? Cq : 0.0;
+      E[q] = live ? Eq : 0.0;
+      D0[q] = live ? Dq0 : 0.0;
+      D1[q] = live ? Dq1 : 0.0;
+      Cp = C[q]; Ep = E[q]; Dp0 = D0[q]; Dp1 = D1[q];
+      if (q % G == G - 1) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  __device__ __forceinline__ void couple(const SegSpan& sp, int n, SegXchg2& X, double& xL0, double& xR0, double& xL1,
+                                         double& xR1) {
+    const int s = sp.s, S = sp.S, l = sp.l;
+    double al = 0.0, be = 0.0, all = 0.0, bel = 0.0, y0 = 0.0, yl0 = 0.0, y1 = 0.0, yl1 = 0.0;
+#pragma unroll
+    for (int q = KR - 1; q >= 0; q--) {
+      const bool last = seg_last(q, n), live = seg_live(q, n);
+      const double aln = E[q] - C[q] * al, ben = -C[q] * be;
+      const double yn0 = D0[q] - C[q] * y0, yn1 = D1[q] - C[q] * y1;
+      y0 = last ? D0[q] : (live ? yn0 : y0);
+      y1 = last ? D1[q] : (live ? yn1 : y1);
+      al = last ? E[q] : (live ? aln : al);
+      be = last ? -C[q] : (live ? ben : be);
+      yl0 = last ? D0[q] : yl0;
+      yl1 = last ? D1[q] : yl1;
+      all = last ? E[q] : all;
+      bel = last ? -C[q] : bel;
+    }
+    X.v[0][s][l] = y0; X.v[1][s][l] = al; X.v[2][s][l] = be;
+    X.v[3][s][l] = yl0; X.v[4][s][l] = all; X.v[5][s][l] = bel;
+    X.v[6][s][l] = y1; X.v[7][s][l] = yl1;
+    __syncthreads();
+    double Qp = 0.0, Qs = 0.0, Vs = 0.0, gb = 1.0;
+    double Pp0 = 0.0, Ps0 = 0.0, Us0 = 0.0, ga0 = 0.0, Pp1 = 0.0, Ps1 = 0.0, Us1 = 0.0, ga1 = 0.0;
+#pragma unroll
+    for (int t = 0; t < kSegMaxS; t++) {
+      if (t < S) {
+        const double af = X.v[1][t][l], bf = X.v[2][t][l], aL = X.v[4][t][l], bL = X.v[5][t][l];
+        const double yf0 = X.v[0][t][l], yL0 = X.v[3][t][l], yf1 = X.v[6][t][l], yL1 = X.v[7][t][l];
+        const double rden = seg_rcp(1.0 - af * Qp);
+        const double Ut0 = (yf0 + af * Pp0) * rden, Ut1 = (yf1 + af * Pp1) * rden;
+        const double Vt = bf * rden;
+        Us0 = t == s ? Ut0 : Us0;
+        Us1 = t == s ? Ut1 : Us1;
+        Vs = t == s ? Vt : Vs;
+        const double gan0 = ga0 + gb * Ut0, gan1 = ga1 + gb * Ut1, gbn = gb * Vt;
+        ga0 = t > s ? gan0 : ga0;
+        ga1 = t > s ? gan1 : ga1;
+        gb = t > s ? gbn : gb;
+        const double Pn0 = yL0 + aL * Pp0 + aL * Qp * Ut0, Pn1 = yL1 + aL * Pp1 + aL * Qp * Ut1;
+        Qp = aL * Qp * Vt + bL;
+        Pp0 = Pn0; Pp1 = Pn1;
+        Ps0 = t == s - 1 ? Pp0 : Ps0;
+        Ps1 = t == s - 1 ? Pp1 : Ps1;
+        Qs = t == s - 1 ? Qp : Qs;
+      }
+      if (t % kSegCoupleGroup == kSegCoupleGroup - 1) __builtin_amdgcn_sched_barrier(0);
+    }
+    xR0 = ga0; xR1 = ga1;
+    xL0 = Ps0 + Qs * (Us0 + Vs * ga0);
+    xL1 = Ps1 + Qs * (Us1 + Vs * ga1);
+  }
+  // back-substitution; x_q is left in D0[q], D1[q]
+  __device__ __forceinline__ void solve(int n, double xL0, double xR0, double xL1, double xR1) {
+    double xn0 = xR0, xn1 = xR1;
+#pragma unroll
+    for (int q = KR - 1; q >= 0; q--) {
+      const double v0 = D0[q] + E[q] * xL0 - C[q] * xn0, v1 = D1[q] + E[q] * xL1 - C[q] * xn1;
+      const bool live = seg_live(q, n);
+      xn0 = live ? v0 : xn0;
+      xn1 = live ? v1 : xn1;
+      D0[q] = live ? v0 : D0[q];
+      D1[q] = live ? v1 : D1[q];
+    }
+  }
+};
+// spline_fc_seg for two value columns f0, f1 over the same layer weights w
+template <int KR>
+__device__ __forceinline__ void spline_fc_seg2(const SegSpan& sg, int N, SegXchg2& X, const double (&w)[KR + 1],
+                                               const double (&f0)[KR], const double (&f1)[KR], double (&fc0)[KR],
+                                               double (&fc1)[KR]) {
+  const int c0 = sg.c0, n = sg.n;
+  const int ns = n + (sg.s == sg.S - 1 ? 1 : 0);
+  SegTri2<KR> T;
+  T.eliminate(ns, [&](int q, double& a, double& bb, double& c, double& d0, double& d1) {
+    const int r = c0 - 1 + q;
+    const int q1 = q + 1 < KR ? q + 1 : KR - 1;
+    const double ai = w[q + 1], bi = 2.0 * (w[q] + w[q + 1]), ci = w[q];
+    const double di0 = 3.0 * (w[q] * f0[q1] + w[q + 1] * f0[q]), di1 = 3.0 * (w[q] * f1[q1] + w[q + 1] * f1[q]);
+    a = r == 0 ? 0.0 : (r == N ? 1.0 : ai);
+    bb = (r == 0 || r == N) ? 1.0 : bi;
+    c = r == 0 ? 1.0 : (r == N ? 0.0 : ci);
+    d0 = r == 0 ? 2.0 * f0[1] : (r == N ? 2.0 * f0[q] : di0);
+    d1 = r == 0 ? 2.0 * f1[1] : (r == N ? 2.0 * f1[q] : di1);
+  });
+  double xL0, xR0, xL1, xR1;
+  T.couple(sg, ns, X, xL0, xR0, xL1, xR1);
+  T.solve(ns, xL0, xR0, xL1, xR1);
+#pragma unroll
+  for (int q = 0; q < KR; q++) {
+    fc0[q] = seg_live(q, ns) ? T.D0[q] : xR0;
+    fc1[q] = seg_live(q, ns) ? T.D1[q] : xR1;
+  }
+}
+
 // SPLINE_UV advective flux of a u (dir 0) / v (dir 1) column at interfaces
 // r = c0-1+q, q = 0..n (0 at the bottom and the surface): FC(r) * 0.5 * the
 // 4-point We average with the reference's masked curvature correction.

@@ -698,6 +698,107 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_
     if (p < n) Tn.st(T.D[p], vs + lev(c0 + p), 0u);   // vs = kBufOff stays beyond the extent
 }
 
+// ---- k_pre_tracer_segb for T and S in one block (Params::t_pair bit 1, in
+// force while Akt(isalt) is Akt(itemp) bit for bit): the spline system is a
+// function of Hz alone and the implicit system of Hz_fwd, Akt and Wi, so one
+// block loads Hz, We, Hz_fwd, Akt, Wi, pm, pn once, factorises both matrices
+// once (SegTri2) and carries the two tracers as two right-hand sides: 11 array
+// passes over both tracers where two blocks of k_pre_tracer_segb make 16, and
+// half the reciprocal chains.  Each tracer's expressions and their order are
+// k_pre_tracer_segb's: bitwise equal to it. ----
+__global__ void __launch_bounds__(kSegBlock, ROMS_PRE_T_SEG_WAVES) k_pre_tracer_segb_pair(Dev d, Range R, PreCoef c,
+                                                                                        int nnew, int nrhs) {
+  const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
+  __shared__ SegXchg2 X;
+  constexpr int KR = kSegRows + 1;
+  const Bounds& b = d.b;
+  const Fields& F = d.f;
+  const int N = b.N;
+  const SegSpan sg = seg_span(N);
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
+  const int iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
+  const bool act = iu >= R.i0 && iu <= R.i1;
+  const int i = act ? iu : (iu < R.i0 ? R.i0 : R.i1), j = R.j0 + (int)bI.y;
+  const long n2 = b.n2, ij = IJ(b, i, j);
+  const int c0 = sg.c0, n = sg.n;
+  const unsigned vo = (unsigned)ij * 8u;
+  auto lev = [&](int k) { return (unsigned)(min(max(k, 1), N) - 1) * (unsigned)n2 * 8u; };
+  auto wlev = [&](int r) { return (unsigned)min(max(r, 1), N - 1) * (unsigned)n2 * 8u; };
+  const BufF64 Hz(F.Hz), Hf(F.c2), We(F.We), Wi(F.Wi);
+  const long ts = 3 * b.n3;   // itemp -> isalt
+  const BufF64 Tr0(F.t + (long)(nrhs - 1) * b.n3), Tn0(F.t + (long)(nnew - 1) * b.n3);
+  const BufF64 Tr1(F.t + (long)(nrhs - 1) * b.n3 + ts), Tn1(F.t + (long)(nnew - 1) * b.n3 + ts);
+  double hz[KR + 1], fl0[KR], fl1[KR];
+  {
+    double tt0[KR], tt1[KR];
+#pragma unroll
+    for (int q = 0; q < KR + 1; q++) {
+      hz[q] = LD(Hz, vo, lev(c0 - 1 + q));
+      if (q < KR) {
+        tt0[q] = LD(Tr0, vo, lev(c0 - 1 + q));
+        tt1[q] = LD(Tr1, vo, lev(c0 - 1 + q));
+      }
+    }
+    spline_fc_seg2<KR>(sg, N, X, hz, tt0, tt1, fl0, fl1);
+  }
+  {
+    double we[KR];
+#pragma unroll
+    for (int q = 0; q < KR; q++) we[q] = LD(We, vo, wlev(c0 - 1 + q));
+#pragma unroll
+    for (int q = 0; q < KR; q++) pin(we[q]);
+#pragma unroll
+    for (int q = 0; q < KR; q++) {
+      const int r = c0 - 1 + q;
+      const bool edge = r == 0 || r == N;
+      fl0[q] = edge ? 0.0 : fl0[q] * we[q];
+      fl1[q] = edge ? 0.0 : fl1[q] * we[q];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int q = 0; q < KR + 1; q++) hz[q] = LD(Hf, vo, lev(c0 - 1 + q));
+  const BufF64 Akt(F.Akt);
+  const BufF64 Pm(F.pm), Pn(F.pn);
+  const double pm = LD(Pm, vo, 0), pn = LD(Pn, vo, 0);
+  const double DC0 = c.dtau * pm * pn;
+  auto fcw = [&](int q, double& fc, double& wc) {
+    const int r = c0 - 1 + q;
+    const unsigned w = wlev(r);
+    const bool in = r > 0 && r < N;
+    const int qa = q + 1 < KR + 1 ? q + 1 : KR;
+    const double f = SEG_DIV(2.0 * c.dtau * LD(Akt, vo, w), hz[qa] + hz[q]);
+    const double wv = DC0 * LD(Wi, vo, w);
+    fc = in ? f : 0.0;
+    wc = in ? wv : 0.0;
+  };
+  double fcl, wcl;
+  fcw(0, fcl, wcl);
+  __syncthreads();  // X reused by the second coupling
+  SegTri2<KR> T;
+  T.eliminate(n, [&](int p, double& a, double& bb, double& cc, double& d0, double& d1) {
+    double fcu, wcu;
+    fcw(p + 1, fcu, wcu);
+    const int p1 = p + 1 < KR ? p + 1 : KR - 1;
+    a = -(fcl + fmax0(wcl));
+    bb = hz[p + 1] + fcu + fmax0(wcu) + fcl - fmin0(wcl);
+    cc = -(fcu - fmin0(wcu));
+    d0 = LD(Tn0, vo, lev(c0 + p)) - c.dtau * pm * pn * (fl0[p1] - fl0[p]);
+    d1 = LD(Tn1, vo, lev(c0 + p)) - c.dtau * pm * pn * (fl1[p1] - fl1[p]);
+    fcl = fcu; wcl = wcu;
+  });
+  double xL0, xR0, xL1, xR1;
+  T.couple(sg, n, X, xL0, xR0, xL1, xR1);
+  T.solve(n, xL0, xR0, xL1, xR1);
+  const unsigned vs = act ? vo : kBufOff;
+#pragma unroll
+  for (int p = 0; p < KR; p++)
+    if (p < n) {   // vs = kBufOff stays beyond the extent
+      Tn0.st(T.D0[p], vs + lev(c0 + p), 0u);
+      Tn1.st(T.D1[p], vs + lev(c0 + p), 0u);
+    }
+}
+
 // kLds (UV_ADV, nrhs == nstp -- always so in the predictor): the spline
 // phase, which loads Hz, Hz of the (i-1)/(j-1) neighbour and u(nrhs) = u(nstp)
 // of every row anyway, also loads u(indx) and leaves in dynamic LDS the row's
@@ -941,6 +1042,15 @@ bool setup_column_kernels(int N) {
   return true;
 }
 
+// one context per host thread, as the shim's (roms_shim.cpp Ctx)
+static thread_local long t_pair_count[2] = {0, 0};
+long t_pair_launches(int bit, long add, bool reset) {
+  if (reset) t_pair_count[0] = t_pair_count[1] = 0;
+  long& c = t_pair_count[bit == kTPairCor ? 1 : 0];
+  c += add;
+  return c;
+}
+
 double pre_step3d_dtau(const Dev& d, const Tlev& t) {
   const double AM3_crv = 1.0 / 6.0;
   return t.iic == t.forw_start ? 0.5 * d.p.dt : d.p.dt * (1.0 - AM3_crv);
@@ -984,7 +1094,11 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   }
   dim3 gt = gridc_of(RI);
   gt.z = b.NT;
-  if (d.p.colseg && d.p.seg_buf)
+  if (d.p.colseg && d.p.seg_buf && (d.p.t_pair & kTPairPre) && b.NT == 2 && b.nTS == 2) {
+    hipLaunchKernelGGL(k_pre_tracer_segb_pair, seg_grid_of(RI, 1), dim3(kCX, seg_waves(b.N)), 0, s, d, RI, c, t.nnew,
+                       t.nrhs);
+    t_pair_launches(kTPairPre, 1);
+  } else if (d.p.colseg && d.p.seg_buf)
     hipLaunchKernelGGL(k_pre_tracer_segb, seg_grid_of(RI, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, RI, c, t.nnew,
                        t.nrhs);
   else if (d.p.colseg)

@@ -536,6 +536,192 @@ __global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb(D
   for (int p = 0; p < KR; p++) Tn.st(T.D[p] * rm, (p < n ? vs : kBufOff) + lev(c0 + p), 0u);   // kBufOff stays beyond the extent
 }
 
+// ---- k_step3d_t_segb for T and S in one block (Params::t_pair bit 2, in
+// force while Akt(isalt) is Akt(itemp) bit for bit; see
+// k_pre_tracer_segb_pair): Hz, We, Akt, Wi, pm, pn, srflx, rmask and ghat are
+// loaded once, both matrices factorised once (SegTri2); t(nrhs), t(nnew),
+// stflx, the pipe sources, the surface row and the KPP terms stay per tracer,
+// selected as kppT / kppS select them in k_step3d_t_segb.  t(nnew) is loaded
+// with the We rows after the spline solve (two tracers' rows held through it
+// would not fit the registers).  Each tracer's expressions and their order
+// are k_step3d_t_segb's: bitwise equal to it. ----
+__global__ void __launch_bounds__(kSegBlock, ROMS_T_SEG_WAVES) k_step3d_t_segb_pair(Dev d, Range R, int nnew, int nrhs) {
+  const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
+  __shared__ SegXchg2 X;
+  constexpr int KR = kSegRows + 1;
+  const Bounds& b = d.b;
+  const Fields& F = d.f;
+  const Params& P = d.p;
+  const int N = b.N;
+  const double dt = P.dt;
+  const SegSpan sg = seg_span(N);
+  auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
+  const int iu = tile_i0(R.i0) + (int)bI.x * kSegCW + sg.col;
+  const bool act = iu >= R.i0 && iu <= R.i1;
+  const int i = act ? iu : (iu < R.i0 ? R.i0 : R.i1), j = R.j0 + (int)bI.y;
+  const long n2 = b.n2, ij = IJ(b, i, j);
+  const int c0 = sg.c0, n = sg.n;
+  const bool last = sg.s == sg.S - 1;
+  const unsigned vo = (unsigned)ij * 8u;
+  auto lev = [&](int k) { return (unsigned)(min(max(k, 1), N) - 1) * (unsigned)n2 * 8u; };
+  auto wlev = [&](int r, int lo, int hi) { return (unsigned)min(max(r, lo), hi) * (unsigned)n2 * 8u; };
+  const BufF64 Hz(F.Hz), We(F.We), Wi(F.Wi);
+  const long ts = 3 * b.n3;   // itemp -> isalt
+  const BufF64 Tr0(F.t + (long)(nrhs - 1) * b.n3), Tn0(F.t + (long)(nnew - 1) * b.n3);
+  const BufF64 Tr1(F.t + (long)(nrhs - 1) * b.n3 + ts), Tn1(F.t + (long)(nnew - 1) * b.n3 + ts);
+  // Hz of the segment's rows waits in LDS from the spline phase to the
+  // diffusion rows, read back through an opaque offset (as k_uv1_segb's Hz
+  // pairs: forwarded, the 15 values stayed in registers and the kernel spilled)
+  __shared__ double sHz[KR + 1][kSegBlock];
+  const int tid = (int)(threadIdx.x + blockDim.x * threadIdx.y);
+  double rhs0[KR], rhs1[KR], pm, pn;
+  {
+    double fl0[KR], fl1[KR];
+    {
+      double hz[KR + 1], tt0[KR], tt1[KR];
+#pragma unroll
+      for (int q = 0; q < KR + 1; q++) {
+        hz[q] = LD(Hz, vo, lev(c0 - 1 + q));
+        if (q < KR) {
+          tt0[q] = LD(Tr0, vo, lev(c0 - 1 + q));
+          tt1[q] = LD(Tr1, vo, lev(c0 - 1 + q));
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < KR + 1; q++) sHz[q][tid] = hz[q];
+      spline_fc_seg2<KR>(sg, N, X, hz, tt0, tt1, fl0, fl1);
+    }
+    double we[KR];
+#pragma unroll
+    for (int q = 0; q < KR; q++) we[q] = LD(We, vo, wlev(c0 - 1 + q, 1, N - 1));
+#pragma unroll
+    for (int p = 0; p < KR; p++) {
+      rhs0[p] = LD(Tn0, vo, lev(c0 + p));
+      rhs1[p] = LD(Tn1, vo, lev(c0 + p));
+    }
+#pragma unroll
+    for (int q = 0; q < KR; q++) pin(we[q]);
+#pragma unroll
+    for (int q = 0; q < KR; q++) {
+      const int r = c0 - 1 + q;
+      const bool edge = r == 0 || r == N;
+      fl0[q] = edge ? 0.0 : fl0[q] * we[q];
+      fl1[q] = edge ? 0.0 : fl1[q] * we[q];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    pm = BufF64(F.pm).ld(vo, 0);
+    pn = BufF64(F.pn).ld(vo, 0);
+#pragma unroll
+    for (int p = 0; p < KR; p++) {
+      const int p1 = p + 1 < KR ? p + 1 : KR - 1;
+      rhs0[p] = rhs0[p] - dt * pm * pn * (fl0[p1] - fl0[p]);
+      rhs1[p] = rhs1[p] - dt * pm * pn * (fl1[p1] - fl1[p]);
+    }
+  }
+  const BufF64 Akt(F.Akt);
+  const double DC0 = dt * pm * pn;
+  const bool kppT = P.lmd, kppS = P.lmd_nonlocal && P.salinity;
+  const double sr = BufF64(F.srflx).ld(vo, 0);
+  const double stf0 = BufF64(F.stflx).ld(vo, 0), stf1 = BufF64(F.stflx).ld(vo, (unsigned)n2 * 8u);
+  if (P.npip > 0) {   // pipe_frc.F sources (step3d_t_ISO.F:927-934)
+    const int pidx = F.pipe_idx[ij];
+    if (pidx > 0) {
+      const double pflx = F.pipe_flx[ij], ptrc0 = F.pipe_trc[pidx - 1], ptrc1 = F.pipe_trc[(pidx - 1) + P.npip];
+#pragma unroll
+      for (int p = 0; p < KR; p++) {
+        const int k = min(c0 + p, N);
+        const double prf = F.pipe_prf[(pidx - 1) + (k - 1) * P.npip];
+        rhs0[p] = rhs0[p] + dt * pm * pn * pflx * prf * ptrc0;
+        rhs1[p] = rhs1[p] + dt * pm * pn * pflx * prf * ptrc1;
+      }
+    }
+  }
+  if (last) {   // the surface cell k = N, row n-1 of the last segment
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int p = 0; p < KR; p++) {
+      t0 = p == n - 1 ? rhs0[p] : t0;
+      t1 = p == n - 1 ? rhs1[p] : t1;
+    }
+    const double swf = BufF64(F.swflx).ld(vo, 0);
+    t0 = t0 + dt * swf * (P.bulk_frc ? BufF64(F.tair).ld(vo, 0) : t0 / LD(Hz, vo, lev(N)));
+    t0 = t0 + dt * stf0;
+    t1 = t1 + dt * stf1;
+#pragma unroll
+    for (int p = 0; p < KR; p++) {
+      rhs0[p] = p == n - 1 ? t0 : rhs0[p];
+      rhs1[p] = p == n - 1 ? t1 : rhs1[p];
+    }
+  }
+  if (kppT || kppS) {
+    // every level's swr_frac / ghat loaded first, outside any data-dependent
+    // branch (k_step3d_t_segb); ghat serves both tracers
+    const BufF64 Sw(F.swr_frac), Gh(F.ghat);
+    const bool nl = P.lmd_nonlocal;
+    double swv[KR + 1], ghv[KR + 1];
+#pragma unroll
+    for (int q = 0; q < KR + 1; q++) {
+      const unsigned o = wlev(c0 - 1 + q, 1, N - 1);
+      swv[q] = kppT ? LD(Sw, vo, o) : 0.0;
+      ghv[q] = LD(Gh, vo, o);
+    }
+    auto termT = [&](int q) { return dt * (sr * swv[q] - (nl ? ghv[q] : 0.0) * (stf0 - sr)); };
+    auto termS = [&](int q) { return -dt * ghv[q] * stf1; };
+    double lo0 = termT(0), lo1 = termS(0);
+#pragma unroll
+    for (int p = 0; p < KR; p++) {
+      const int k = min(c0 + p, N);
+      const double up0 = termT(p + 1), up1 = termS(p + 1);
+      double t0 = rhs0[p], t1 = rhs1[p];
+      t0 = k <= N - 1 ? t0 + up0 : t0;
+      t0 = k >= 2 ? t0 - lo0 : t0;
+      t1 = k <= N - 1 ? t1 + up1 : t1;
+      t1 = k >= 2 ? t1 - lo1 : t1;
+      rhs0[p] = kppT ? t0 : rhs0[p];
+      rhs1[p] = kppS ? t1 : rhs1[p];
+      lo0 = up0; lo1 = up1;
+    }
+  }
+  int tl = tid;
+  __asm__ volatile("" : "+v"(tl));
+  auto HZ = [&](int q) { return sHz[q][tl]; };
+  auto fcw = [&](int q, double& fc, double& wc) {   // interface c0-1+q
+    const int r = c0 - 1 + q;
+    const unsigned w = wlev(r, 1, N - 1);
+    const bool in = r > 0 && r < N;
+    const int qa = q + 1 < KR + 1 ? q + 1 : KR;
+    const double f = SEG_DIV(2.0 * dt * LD(Akt, vo, w), HZ(q) + HZ(qa));
+    const double c = DC0 * LD(Wi, vo, w);
+    fc = in ? f : 0.0;
+    wc = in ? c : 0.0;
+  };
+  double fcl, wcl;
+  fcw(0, fcl, wcl);
+  __syncthreads();  // X reused by the second coupling
+  SegTri2<KR> T;
+  T.template eliminate<ROMS_SEG_T_GROUP>(n, [&](int p, double& a, double& bb, double& c, double& d0, double& d1) {
+    double fcu, wcu;
+    fcw(p + 1, fcu, wcu);
+    a = -(fcl + fmax0(wcl));
+    bb = HZ(p + 1) + fcu + fmax0(wcu) + fcl - fmin0(wcl);
+    c = -(fcu - fmin0(wcu));
+    d0 = rhs0[p];
+    d1 = rhs1[p];
+    fcl = fcu; wcl = wcu;
+  });
+  double xL0, xR0, xL1, xR1;
+  T.couple(sg, n, X, xL0, xR0, xL1, xR1);
+  T.solve(n, xL0, xR0, xL1, xR1);
+  const double rm = BufF64(F.rmask).ld(vo, 0);
+  const unsigned vs = act ? vo : kBufOff;
+#pragma unroll
+  for (int p = 0; p < KR; p++) {   // kBufOff stays beyond the extent (k_step3d_t_segb)
+    const unsigned o = (p < n ? vs : kBufOff) + lev(c0 + p);
+    Tn0.st(T.D0[p] * rm, o, 0u);
+    Tn1.st(T.D1[p] * rm, o, 0u);
+  }
+}
+
 void setup_column_kernels_t(size_t bytes) {
   (void)hipFuncSetAttribute((const void*)k_step3d_t_v<ColLds>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)bytes);
@@ -585,7 +771,10 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
     gt.z = b.NT;
     if (d.p.colseg) {
       ktimer_mark(s, kTimedStep3dTSeg, 0);
-      if (d.p.seg_buf)
+      if (d.p.seg_buf && (d.p.t_pair & kTPairCor) && b.NT == 2 && b.nTS == 2) {
+        hipLaunchKernelGGL(k_step3d_t_segb_pair, seg_grid_of(r, 1), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
+        t_pair_launches(kTPairCor, 1);
+      } else if (d.p.seg_buf)
         hipLaunchKernelGGL(k_step3d_t_segb, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);
       else
         hipLaunchKernelGGL(k_step3d_t_seg, seg_grid_of(r, b.NT), dim3(kCX, seg_waves(b.N)), 0, s, d, r, t.nnew, t.nrhs);

@@ -94,7 +94,11 @@ struct Params {
   // vgrid2 took the first of the eight: further VGrid kernels (ROMS_GPU_VGRID2 bits, 0: the streaming forms):
   // 1 k_omega_seg, 2 k_set_huv1_chain, 4 k_uv2_fused, 8 k_visc3d_stg, 16 k_t3dmix_stg.  In force as bits 8.. of vg.
   int vgrid2;
-  int reserved_[7];
+  // t_pair took the second: tracer segment solvers that carry T and S as two right-hand sides of one block
+  // (ROMS_GPU_T_PAIR bits: 1 k_pre_tracer_segb_pair, 2 k_step3d_t_segb_pair).  The bits in force: the configured mask while Akt(isalt) is
+  // Akt(itemp) bit for bit (the shim's akt_same flag, set by lmd_vmix, cleared by a host write of Akt), else 0.
+  int t_pair;
+  int reserved_[6];
   // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
@@ -236,6 +240,9 @@ constexpr int kVgDefault = kVgRho | kVgKppExt | kVgHuv;   // k_kpp_int measured 
 // Params::vgrid2 bits; in Params::vg they stand kVg2Shift higher
 constexpr int kVg2Omega = 1, kVg2Huv1 = 2, kVg2Uv2 = 4, kVg2Visc = 8, kVg2T3dmix = 16, kVg2All = 31, kVg2Shift = 8;
 constexpr int kVg2Default = kVg2All;  // profiles/r10_vgrid_rest_ab.txt
+// Params::t_pair bits (ROMS_GPU_T_PAIR)
+constexpr int kTPairPre = 1, kTPairCor = 2, kTPairAll = 3;
+constexpr int kTPairDefault = kTPairAll;
 struct VGrid {
   const double *Cs_w, *Cs_r;
   double z, h, hinv, hc, ds;
@@ -491,6 +498,10 @@ int s2d_edge_mode(const Dev& d);
 // took closed-edge mode m (launch_fast_step, on the bounds a multi-rank fast
 // step widens: the mode can differ from one fast step to the next)
 int s2d_edge_modes_taken(bool reset = false);
+// pair-form tracer solver launches of this host thread since the last reset,
+// per Params::t_pair bit (kTPairPre or kTPairCor; add: count `add` launches
+// of `bit`); a replayed graph counts the launches of its capture only
+long t_pair_launches(int bit, long add = 0, bool reset = false);
 bool prsgrd_takes_strips(const Dev& d, bool with_uv, int& jA, int& jB, int& nstrip);
 double pre_step3d_dtau(const Dev& d, const Tlev& t);   // pre_step3d's dtau (k_pre_step3d.hip)
 void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx);

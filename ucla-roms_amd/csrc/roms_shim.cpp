@@ -68,6 +68,14 @@ struct Ctx {
   // -- a host that brings its own Hz keeps the streaming forms.  Params::vg
   // follows it (vg_set).
   bool vgrid_valid = false;
+  // Akt(isalt) is Akt(itemp) bit for bit over the interior: what lmd_vmix
+  // leaves without LMD_DDMIX when the two background values are the same bits
+  // (k_kpp_int: Ks starts as Kt and every later operation on it mirrors Kt's
+  // on the same operands).  Set by every lmd_vmix launch, cleared when the
+  // host writes Akt through any entry; while it holds the tracer solvers of
+  // Params::t_pair carry T and S over one matrix (akt_set).
+  bool akt_same = false;
+  int t_pair_cfg = 0;   // ROMS_GPU_T_PAIR as read at init
   std::string err;
   // graph cache: key = (nstp, knew at step start)
   std::map<long, hipGraphExec_t> graphs;
@@ -147,8 +155,20 @@ void vg_set(bool valid) {
   g.vgrid_valid = valid;
   g.d.p.vg = valid ? (short)(g.d.p.vgrid | (g.d.p.vgrid2 << kVg2Shift)) : (short)0;
 }
-// the host wrote field `id`: Hz, z_r, z_w, h, hinv or a Cs table ends VGrid's validity
+void akt_set(bool same) {
+  g.akt_same = same;
+  g.d.p.t_pair = same ? g.t_pair_cfg : 0;
+}
+// lmd_vmix was launched: its Akt(isalt) is its Akt(itemp) unless LMD_DDMIX or unequal backgrounds part them
+void akt_lmd_done() {
+  const Params& P = g.d.p;
+  akt_set(g.cfg.lmd_mixing && !P.lmd_ddmix && g.d.b.nTS == 2 &&
+          std::memcmp(&P.Akt_bak[0], &P.Akt_bak[1], sizeof(double)) == 0);
+}
+// the host wrote field `id`: Hz, z_r, z_w, h, hinv or a Cs table ends VGrid's validity,
+// Akt the equality of its two slots (captured steps form both anew before they read either)
 void vg_host_write(int id) {
+  if (id == ROMS_Akt) akt_set(false);
   if (id != ROMS_Hz && id != ROMS_z_r && id != ROMS_z_w && id != ROMS_h && id != ROMS_hinv && id != ROMS_Cs_w &&
       id != ROMS_Cs_r)
     return;
@@ -510,14 +530,14 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   // none of set_HUV's or omega's outputs, so on a multi-rank run it goes first
   // and covers set_HUV's exchange (Akv, Akt, hbls, hbbl follow on the halo stream)
   const bool lmd_early = xo && g.cfg.lmd_mixing;
-  if (lmd_early) TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nstp)));
+  if (lmd_early) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nstp))); akt_lmd_done(); }
   XJOIN_T(1, x_huv);   // omega reads FlxU(iend+1), FlxV(jend+1)
   // the predictor's omega also forms pre_step3d's Hz_bak/Hz_fwd (nothing in
   // between -- lmd_vmix, prsgrd -- writes FlxU, FlxV, Hz, We or Wi)
   bool hb_done = false;
   TIMED(ROMS_R_OMEGA, DEFER(hb_done = launch_omega(d, s, T, d.p.omega_hb && d.p.hoist && T.nrhs != 3 ?
                                                                  0.5 * pre_step3d_dtau(d, T) : 0.0)));
-  if (g.cfg.lmd_mixing && !lmd_early) TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp));
+  if (g.cfg.lmd_mixing && !lmd_early) { TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp)); akt_lmd_done(); }   // (d is g.d)
   // the horizontal momentum r.h.s. of pre_step3d / step3d_uv1 rides in the
   // prsgrd kernel just before them (prsgrd_can_fuse_uv; nothing between the
   // two touches u, v(nrhs), FlxU, FlxV, Hz or ru, rv); it reads neither We, Wi
@@ -546,7 +566,7 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   }
   frc_step_phase(d, s, 2, pot);     // set_forces, '1/2 fwd' (main.F:433)
   launch_bulk_flux(d, s, T.nrhs);   // set_forces (main.F:433): BULK_FRC only
-  if (g.cfg.lmd_mixing) TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs)));   // Akv, Akt, hbls, hbbl
+  if (g.cfg.lmd_mixing) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs))); akt_lmd_done(); }   // Akv, Akt, hbls, hbbl
   frc_step_phase(d, s, 3, pot);     // set_bry_all 'forward' + set_tides (main.F:438-441)
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 1 : -1, p_ready));
   XJOIN_T(16, xt);   // step3d_uv1 reads We and Akv across the halo
@@ -886,6 +906,13 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   P.vgrid2 = env_int("ROMS_GPU_VGRID2", kVg2Default, 0, kVg2All);
   P.vg = 0;
   g.vgrid_valid = false;
+  // T and S as two right-hand sides of one block in the tracer segment solvers
+  // (bits in roms_dev.h), in force while Akt's two slots are equal (akt_same);
+  // ROMS_GPU_T_PAIR=0 for one block per tracer
+  g.t_pair_cfg = env_int("ROMS_GPU_T_PAIR", kTPairDefault, 0, kTPairAll);
+  P.t_pair = 0;
+  g.akt_same = false;
+  (void)t_pair_launches(0, 0, true);
   P.hoist = !env_off("ROMS_GPU_HOIST");
   // default on: C3 prsgrd 3.62-3.63 -> 3.55 ms per call (r5_d_seg_buf_chunk_prs_ab.txt)
   P.prs_buf = !env_off("ROMS_GPU_PRS_BUF");
@@ -1170,6 +1197,12 @@ int roms_gpu_vgrid2(void) {
   return g.d.p.vgrid2 + (g.vgrid_valid ? 256 : 0);
 }
 
+int roms_gpu_tracer_pair(long launches[2]) {
+  REQUIRE_INIT_NOJOIN();
+  if (launches) { launches[0] = t_pair_launches(kTPairPre); launches[1] = t_pair_launches(kTPairCor); }
+  return g.t_pair_cfg + (g.akt_same ? 256 : 0);
+}
+
 int roms_gpu_vgrid_check(long out[3]) {
   REQUIRE_INIT_RO();
   if (!out) { g.err = "roms_gpu_vgrid_check: null argument"; return -1; }
@@ -1232,6 +1265,7 @@ int roms_gpu_lmd_vmix(int tind, const roms_tlev* t) {
   if (!g.cfg.lmd_mixing) { g.err = "roms_gpu_lmd_vmix: library initialised without lmd_mixing"; return -4; }
   if (tind < 1 || tind > 3) { g.err = "roms_gpu_lmd_vmix: bad time index"; return -1; }
   launch_lmd_vmix(g.d, g.s, to_tlev(t), tind);
+  akt_lmd_done();
   return post_launch();
 }
 int roms_gpu_swr_frac(const roms_tlev* t) {
@@ -1443,6 +1477,7 @@ int roms_gpu_step(roms_tlev* t) {
   // replay; advance the host-side indices exactly as enqueue_step would
   CHECK_HIP(hipGraphLaunch(it->second, g.s));
   vg_set(true);   // the replayed step ran set_depth
+  if (g.cfg.lmd_mixing) akt_lmd_done();   // and lmd_vmix
   t->nrhs = 3;
   t->nnew = 3 - t->nstp;
   g.rho_slot = t->nnew;   // the replayed step ended with rho_eos(nnew)

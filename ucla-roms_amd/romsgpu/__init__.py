@@ -568,6 +568,17 @@ class Model:
         self._chk(min(r, 0), "vgrid2")
         return r % 256, bool(r // 256)
 
+    def tracer_pair(self):
+        """(mask, same, (pre, cor)): the tracer segment solvers that carry T
+        and S in one block (ROMS_GPU_T_PAIR, as read at init: 1 pre_step3d,
+        2 step3d_t), whether Akt(isalt) is known to equal Akt(itemp) so that
+        they do, and the pair-form launches of the two routines enqueued since
+        init (roms_gpu_tracer_pair)."""
+        n = (ctypes.c_long * 2)(0, 0)
+        r = self.L.roms_gpu_tracer_pair(n)
+        self._chk(min(r, 0), "tracer_pair")
+        return r % 256, bool(r // 256), (n[0], n[1])
+
     def vgrid_mismatch(self):
         """(z_w, z_r, Hz): stored values that differ bitwise from the ones
         formed from the kept free surface, h and hinv, over set_depth's range
