@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 22
+#define ROMS_GPU_ABI_VERSION 23
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -365,6 +365,23 @@ int roms_gpu_vgrid_check(long out[3]);
  * pre_step3d and of step3d_t this host thread enqueued since init (a replayed
  * graph counts those of its capture).                                        */
 int roms_gpu_tracer_pair(long launches[2]);
+/* The horizontal tracer kernels of pre_step3d and step3d_t as level walks
+ * (ABI 23).  With two tracers the kernels of ROMS_GPU_T_HSTG (read at init; a
+ * mask, default 7 with the segment solvers and 2 with the column solvers of
+ * N <= 63, 0 for one block per 64x4 tile and level) run one block per
+ * 64x8 cells over all levels: the lane's masks, pm, pn once per block, each
+ * level's FlxU, FlxV, T, S windows staged in LDS with the next level's in
+ * flight and half the halo rows of the 64x4 tiles, every field keeping its
+ * bits:
+ *   1  k_pre_tracer_stg (pre_step3d)   2  k_step3d_t_stg (step3d_t)
+ *   4  k_pre_tracer_stg forms Hz from the kept free surface instead of
+ *      reading it, while the grid is valid (roms_gpu_vgrid)
+ * NT = 1 keeps the per-level kernels.
+ * roms_gpu_tracer_hstg returns mask + 256 * (grid valid), negative before
+ * init; launches[0..2] (if not NULL) get the launches of k_pre_tracer_stg, of
+ * k_step3d_t_stg and of the k_pre_tracer_stg that formed Hz which this host
+ * thread enqueued since init (a replayed graph counts those of its capture). */
+int roms_gpu_tracer_hstg(long launches[3]);
 /* Which horizontal paths this rank's model runs, chosen from Lm, Mm, its
  * edges and the ROMS_GPU_* switches by the same host functions the launchers
  * call:

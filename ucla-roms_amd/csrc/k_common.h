@@ -285,6 +285,143 @@ __device__ __forceinline__ double tracer_fe(const Bounds& b, const A& a, int i, 
   return 0.5 * (a.t(i, m) + a.t(i, m - 1) - 0.3333333333333333 * (g0 - gm)) * Fl;
 }
 
+// ---- the staged level walk of the horizontal tracer kernels for two tracers
+// (k_pre_tracer_stg, k_step3d_t_stg): one block per tile of cells walks k = 1..N.
+// A lane's umask / vmask values are read once per block; each level's FlxU,
+// FlxV, T(nrhs), S(nrhs) windows go to LDS from registers while the next
+// level's are in flight (the form of k_t3dmix_stg).  A thread's kTSR window
+// entries are the same cells of all four fields.  A lane reads its stencil of
+// the windows once per level and forms the four faces from it
+// (tracer_stg_fluxes) instead of once per face through an accessor.  Every global access of the
+// walk is a buffer access (BufF64): the thread's 32-bit byte offset in a
+// level's plane plus the level's scalar offset, so no 64-bit address per
+// entry lives across the levels, and an entry outside the arrays (kBufOff)
+// reads 0 without a branch. ----
+// The block is kBX x kTSY cells, kTSY a multiple of the 64x4 tiles' kBY: the
+// window's four halo rows are fetched once per kTSY rows instead of once per
+// four.  Measured at C3 (profiles/r13_tracer_stg_ab.txt): at 4 rows the two
+// kernels moved 14.4 and 9.6 GB per launch against the per-level tiles' 13.7
+// and 10.2, at 8 rows 11.8 and 7.8; the step with 4 / 8 / 16 rows 41.9-42.5 /
+// 40.8-41.3 / 41.0-41.6 ms against the parent's 42.4-42.8 in one alternation.
+#ifndef ROMS_T_HSTG_ROWS
+#define ROMS_T_HSTG_ROWS 8
+#endif
+constexpr int kTSWaves = 4;   // waves per SIMD the two kernels are compiled for: 109-123 VGPRs, no spill (profiles/r13_resource_usage.txt)
+constexpr int kTSY = ROMS_T_HSTG_ROWS, kTSB = kBX * kTSY;   // rows and threads per block
+constexpr int kTSN = kUVW * (kTSY + 4);                      // entries of one window
+constexpr int kTSR = (kTSN + kTSB - 1) / kTSB;
+inline dim3 grid_tstg(const Range& r) {
+  int ni = r.i1 - tile_i0(r.i0) + 1, nj = r.j1 - r.j0 + 1;
+  if (ni < 1) ni = 1;
+  if (nj < 1) nj = 1;
+  return dim3((ni + kBX - 1) / kBX, (nj + kTSY - 1) / kTSY, 1);
+}
+struct TracerStg {
+  double L[4][kTSN];   // FlxU, FlxV, T, S of the level
+  __device__ __forceinline__ void put(int tid, const double (&w)[4][kTSR]) {
+#pragma unroll
+    for (int r = 0; r < kTSR; r++) {
+      const int q = tid + r * kTSB;
+      if (q < kTSN) {
+#pragma unroll
+        for (int f = 0; f < 4; f++) L[f][q] = w[f][r];
+      }
+    }
+  }
+};
+// a thread's entries of the level windows: the byte offset of each in a level's plane (kBufOff: none, or outside the arrays)
+struct TracerStgLd {
+  unsigned o[kTSR];
+  __device__ __forceinline__ TracerStgLd(const Bounds& b, int ib, int jb, int tid) {
+#pragma unroll
+    for (int r = 0; r < kTSR; r++) {
+      const int q = tid + r * kTSB;
+      const int i = ib + q % kUVW, j = jb + q / kUVW;
+      const bool ok = q < kTSN && i >= -1 && i <= b.Lm + 2 && j >= -1 && j <= b.Mm + 2;
+      o[r] = ok ? (unsigned)IJ(b, i, j) * 8u : kBufOff;
+    }
+  }
+  // lev: the level's byte offset (k-1)*n2*8
+  __device__ __forceinline__ void ld(const BufF64& FU, const BufF64& FV, const BufF64& T0, const BufF64& T1, unsigned lev,
+                                     double (&w)[4][kTSR]) const {
+#pragma unroll
+    for (int r = 0; r < kTSR; r++) {
+      w[0][r] = FU.ld(o[r], lev);
+      w[1][r] = FV.ld(o[r], lev);
+      w[2][r] = T0.ld(o[r], lev);
+      w[3][r] = T1.ld(o[r], lev);
+    }
+  }
+};
+
+// The two faces c and c+1 of a cell along one direction (tracer_fx at m = i
+// and i + 1, or tracer_fe at m = j and j + 1) from the cell's own stencil read
+// once: T[q] = t(c-2+q), M[q] = mask(c-1+q), F0 / F1 the volume fluxes of the
+// faces, [lo, hi] the clamp of tracer_fx / tracer_fe.  The elementary
+// difference (t(p) - t(p-1)) * mask(p) of a point p is one expression whichever
+// face asks for it, so the four of p = c-1..c+2 are formed once; for a cell
+// with lo <= c <= hi - 1 (every cell the tracer kernels store) the clamp can
+// only turn face c's p = c-1 into c and face c+1's p = c+2 into c+1.  The
+// faces' own expressions are tracer_fx's in its order: bit-identical to it.
+__device__ __forceinline__ double tracer_face(double el0, double el1, double el2, double tm, double tm1, double Fl,
+                                              bool upstream) {
+  if (upstream) {
+    const double cm = el1 - el0, c0 = el2 - el1;   // curv(m-1), curv(m)
+    return 0.5 * (tm + tm1) * Fl - 0.1666666666666666 * (cm * fmax0(Fl) + c0 * fmin0(Fl));
+  }
+  const double gm = 0.5 * (el1 + el0), g0 = 0.5 * (el2 + el1);  // grad(m-1), grad(m)
+  return 0.5 * (tm + tm1 - 0.3333333333333333 * (g0 - gm)) * Fl;
+}
+__device__ __forceinline__ void tracer_face_pair(int lo, int hi, int c, const double (&T)[5], const double (&M)[4],
+                                                 double F0, double F1, bool upstream, double& X0, double& X1) {
+  double E[4];
+#pragma unroll
+  for (int q = 0; q < 4; q++) E[q] = (T[q + 1] - T[q]) * M[q];
+  const double a0 = c - 1 < lo ? E[1] : E[0];   // face c, p = clamp(c-1)
+  const double b2 = c + 2 > hi ? E[2] : E[3];   // face c+1, p = clamp(c+2)
+  X0 = tracer_face(a0, E[1], E[2], T[2], T[1], F0, upstream);
+  X1 = tracer_face(E[1], E[2], b2, T[3], T[2], F1, upstream);
+}
+// a lane's masks of both directions, umask(i-1..i+2, j) and vmask(i, j-1..j+2): the same at every level, read once
+struct TracerStgMask {
+  double UM[4], VM[4];
+  __device__ __forceinline__ TracerStgMask(const Bounds& b, const Fields& F, long ij) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      UM[q] = F.umask[ij - 1 + q];
+      VM[q] = F.vmask[ij + (q - 1) * (long)b.nx2];
+    }
+  }
+};
+// a lane's volume fluxes of the level's staged windows (TracerStg), cw its cell: FlxU(i), FlxU(i+1), FlxV(j), FlxV(j+1)
+struct TracerStgFlx {
+  double FU[2], FV[2];
+  __device__ __forceinline__ TracerStgFlx(const TracerStg& W, int cw) {
+    FU[0] = W.L[0][cw]; FU[1] = W.L[0][cw + 1];
+    FV[0] = W.L[1][cw]; FV[1] = W.L[1][cw + kUVW];
+  }
+};
+// tracer t's four fluxes of the cell (i, j): FX0, FX1 = tracer_fx(i), tracer_fx(i + 1), FE0, FE1 likewise.
+// Precondition (tracer_face_pair's clamp): istr <= i <= iend and jstr <= j <= jend, i.e. a cell of the
+// routines' interior ranges; for any other lane (past the range, the predictor's ring) the values are
+// not tracer_fx's and must not be stored.  The flux expressions live in tracer_fx / tracer_fe and in
+// tracer_face: a change of one is a change of the other (tests/test_gpu_tracer_stg.py compares them bitwise).
+__device__ __forceinline__ void tracer_stg_fluxes(const Bounds& b, const TracerStg& W, const TracerStgMask& M,
+                                                  const TracerStgFlx& S, int t, int cw, int i, int j, bool upstream,
+                                                  double& FX0, double& FX1, double& FE0, double& FE1) {
+  const double* T = W.L[2 + t];
+  double TX[5], TY[5];
+#pragma unroll
+  for (int q = 0; q < 5; q++) {
+    TX[q] = T[cw - 2 + q];
+    TY[q] = q == 2 ? TX[2] : T[cw + (q - 2) * kUVW];
+  }
+  tracer_face_pair(b.west_edge ? b.istr : -1000000, b.east_edge ? b.iend + 1 : 1000000, i, TX, M.UM, S.FU[0], S.FU[1],
+                   upstream, FX0, FX1);
+  tracer_face_pair(b.south_edge ? b.jstr : -1000000, b.north_edge ? b.jend + 1 : 1000000, j, TY, M.VM, S.FV[0], S.FV[1],
+                   upstream, FE0, FE1);
+}
+
 // Stage the (kUVW x kUVH) window around a block's 64x4 tile: the level-k
 // fluxes and the masks (once), then per tracer the tracer field.
 struct TracerWin {

@@ -163,6 +163,125 @@ __global__ void __launch_bounds__(kBX * kBY) k_pre_tracer_h1(Dev d, Range R, Pre
   }
 }
 
+// ---- the same for two tracers as one block per tile walking the levels
+// (Params::t_hstg bit kTHstgPre; TracerStg, k_common.h): the lane's masks, pm,
+// pn and the river tests once per block instead of once per level; each
+// level's FlxU, FlxV, T, S windows in flight a level ahead, the lane's stencil
+// read from them once for its four faces (tracer_stg_fluxes); the lane's own
+// inputs (Hz_bak from omega or We, Wi of the level's upper face, t(nstp),
+// t(indx)) loaded at the top of their level.  The pseudo-continuity fluxes of
+// the lane's faces are the window's entries, We, Wi of the lower face the
+// previous level's upper ones.
+// VG (bit kTHstgHz in force): Hz of the lane's cell from VGrid, z_w carried
+// up the levels and Cs_w read a level ahead, instead of the stored Hz.
+// Lanes past the range walk too (barriers) and store nothing.  Per level the
+// expressions of k_pre_tracer_h1<2, kHB> in their order: bit-identical. ----
+template <bool kHB, bool VG>
+__global__ void __launch_bounds__(kTSB, kTSWaves) k_pre_tracer_stg(Dev d, Range R, PreCoef c, int nstp, int nnew, int nrhs) {
+  const uint3 bI = xcd_tile();
+  __shared__ TracerStg W;
+  const Bounds& b = d.b;
+  const Fields& F = d.f;
+  const int N = b.N, indx = 3 - nstp;
+  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * kTSY;
+  const int ib = i0 - 2, jb = j0 - 2;
+  const long n2 = b.n2;
+  const int tid = threadIdx.x + kBX * threadIdx.y;
+  const TracerStgLd E(b, ib, jb, tid);
+  const long ts = 3 * b.n3;   // itemp -> isalt
+  const BufF64 FU(F.FlxU), FV(F.FlxV);
+  const BufF64 Tr0(F.t + (long)(nrhs - 1) * b.n3), Tr1(F.t + (long)(nrhs - 1) * b.n3 + ts);
+  const BufF64 Ts0(F.t + (long)(nstp - 1) * b.n3), Ts1(F.t + (long)(nstp - 1) * b.n3 + ts);
+  const BufF64 Ti0(F.t + (long)(indx - 1) * b.n3), Ti1(F.t + (long)(indx - 1) * b.n3 + ts);
+  const BufF64 Tn0(F.t + (long)(nnew - 1) * b.n3), Tn1(F.t + (long)(nnew - 1) * b.n3 + ts);
+  const BufF64 C2(F.c2), C3(F.c3), Hz(F.Hz), We(F.We), Wi(F.Wi);
+  const unsigned ls = (unsigned)n2 * 8u;   // a level's bytes
+  double w[4][kTSR];
+  E.ld(FU, FV, Tr0, Tr1, 0u, w);
+  const int i = i0 + (int)threadIdx.x, j = j0 + (int)threadIdx.y;
+  const bool act = i >= R.i0 && i <= R.i1 && j <= R.j1;
+  const bool in = act && i >= b.istr && j >= b.jstr;
+  const bool formed = kHB && in;   // Hz_bak/fwd from omega
+  const long ij = act ? IJ(b, i, j) : IJ(b, R.i0, R.j0);
+  const unsigned vo = (unsigned)ij * 8u;
+  // lanes past the range, the ring's lanes for the tracers and the interior's for c2 / c3 under kHB store nothing
+  const unsigned vin = in ? vo : kBufOff, vhb = act && !formed ? vo : kBufOff;
+  double we0 = 0.0, wi0 = 0.0;   // We, Wi of the level's lower face
+  if (!formed) { we0 = F.We[ij]; wi0 = F.Wi[ij]; }
+  double gz = 0.0, gh = 0.0, gi = 0.0, gw = 0.0, csw = 0.0;   // VG: z_sd, h, hinv, z_w(k-1), Cs_w(k)
+  if constexpr (VG) {
+    gz = F.z_sd[ij]; gh = F.h[ij]; gi = F.hinv[ij];
+    gw = -gh;   // VGrid::zw0
+    csw = F.Cs_w[1];
+  }
+  const double pm = F.pm[ij], pn = F.pn[ij];
+  const TracerStgMask M(b, F, ij);
+  // river inflow faces of the lane's cell (river_tracer_flux's own test, once)
+  bool rx0 = false, rx1 = false, re0 = false, re1 = false;
+  if (d.p.nriv > 0 && in) {
+    rx0 = fabs(F.riv_uflx[ij]) > 1e-3; rx1 = fabs(F.riv_uflx[ij + 1]) > 1e-3;
+    re0 = fabs(F.riv_vflx[ij]) > 1e-3; re1 = fabs(F.riv_vflx[ij + b.nx2]) > 1e-3;
+  }
+  const bool riv = rx0 || rx1 || re0 || re1;
+  const int cw = (int)threadIdx.x + 2 + ((int)threadIdx.y + 2) * kUVW;   // the lane's cell in the windows
+  unsigned lev = 0u;   // (k-1)*n2*8
+  for (int k = 1; k <= N; k++, lev += ls) {
+    // the lane's own inputs of this level: they land under the barriers and
+    // the fluxes (held a level ahead they need a second register set and a
+    // copy per level, which waits for every load in flight)
+    double x1, y1 = 0.0;   // Hz_bak from omega, or We, Wi of the level's upper face
+    if (formed) {
+      x1 = C3.ld(vo, lev);
+    } else {
+      x1 = We.ld(vo, lev + ls); y1 = Wi.ld(vo, lev + ls);
+    }
+    double hz;
+    if constexpr (!VG) hz = Hz.ld(vo, lev);
+    const double tsk0 = Ts0.ld(vo, lev), tsk1 = Ts1.ld(vo, lev), tik0 = Ti0.ld(vo, lev), tik1 = Ti1.ld(vo, lev);
+    const double cs = csw;
+    if constexpr (VG) csw = F.Cs_w[min(k + 1, N)];   // a level ahead
+    if (k > 1) __syncthreads();   // the previous level's windows consumed
+    W.put(tid, w);
+    if (k < N) E.ld(FU, FV, Tr0, Tr1, lev + ls, w);
+    if constexpr (VG) {   // under the loads
+      const double z = vg_make(d, gz, gh, gi).zw1(k, cs);
+      hz = z - gw;
+      gw = z;
+    }
+    __syncthreads();
+    const TracerStgFlx S(W, cw);
+    double hb = x1;
+    if (!formed) {
+      const double fu0 = S.FU[0], fu1 = S.FU[1], fv0 = S.FV[0], fv1 = S.FV[1];
+      const double we1 = x1, wi1 = y1;
+      const double cff = 0.5 * c.dtau;
+      const double FlxDiv = cff * pm * pn * (fu1 - fu0 + fv1 - fv0 + we1 + wi1 - we0 - wi0);
+      hb = hz + FlxDiv;
+      const double hf = hz - FlxDiv;
+      C2.st(hf, vhb, lev);  // Hz_fwd, Hz_bak kept for the column solves (range istr-1.., jstr-1..)
+      C3.st(hb, vhb, lev);
+      we0 = we1; wi0 = wi1;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+      const int itrc = t + 1;
+      double FX0, FX1, FE0, FE1;   // `in` lanes lie in istr..iend x jstr..jend (tracer_stg_fluxes' precondition); ring lanes store no tracer
+      tracer_stg_fluxes(b, W, M, S, t, cw, i, j, false, FX0, FX1, FE0, FE1);
+      if (riv) {   // river inflow faces (compute_horiz_tracer_fluxes.h:217-246)
+        int kr = k, ir = i, jr = j;   // opaque: the faces' addresses are formed here, not carried up the levels by every lane
+        __asm__ volatile("" : "+s"(kr), "+v"(ir), "+v"(jr));
+        if (rx0) river_tracer_flux(d, 0, ir, jr, kr, itrc, FX0);
+        if (rx1) river_tracer_flux(d, 0, ir + 1, jr, kr, itrc, FX1);
+        if (re0) river_tracer_flux(d, 1, ir, jr, kr, itrc, FE0);
+        if (re1) river_tracer_flux(d, 1, ir, jr + 1, kr, itrc, FE1);
+      }
+      const double tsk = t == 0 ? tsk0 : tsk1, tik = t == 0 ? tik0 : tik1;
+      (t == 0 ? Tn0 : Tn1).st(hb * (c.cf_stp * tsk + c.cf_bak * tik) - c.dtau * pm * pn * (FX1 - FX0 + FE1 - FE0), vin, lev);
+      (t == 0 ? Ti0 : Ti1).st(hz * tsk, vin, lev);
+    }
+  }
+}
+
 // ---- tracers, vertical part per column: spline advection on t(nrhs), then
 // implicit diffusion with Wi up-winding on Hz_fwd (LDS slots A, B). ----
 template <class C>
@@ -1051,6 +1170,14 @@ long t_pair_launches(int bit, long add, bool reset) {
   return c;
 }
 
+static thread_local long t_hstg_count[3] = {0, 0, 0};
+long t_hstg_launches(int bit, long add, bool reset) {
+  if (reset) t_hstg_count[0] = t_hstg_count[1] = t_hstg_count[2] = 0;
+  long& c = t_hstg_count[bit == kTHstgCor ? 1 : bit == kTHstgHz ? 2 : 0];
+  c += add;
+  return c;
+}
+
 double pre_step3d_dtau(const Dev& d, const Tlev& t) {
   const double AM3_crv = 1.0 / 6.0;
   return t.iic == t.forw_start ? 0.5 * d.p.dt : d.p.dt * (1.0 - AM3_crv);
@@ -1071,7 +1198,20 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   // the rows strips cover (k_tracer_strip.hip), the rest on tiles
   auto horiz_tiles = [&](const Range& rh) {
     const dim3 gh = grid3_of(rh, b.N), bh(kBX, kBY);
-    if (d.p.hoist && b.NT == 2 && hb_done)
+    if (d.p.hoist && b.NT == 2 && (d.p.t_hstg & kTHstgPre)) {
+      const bool vg = (d.p.t_hstg & kTHstgHz) != 0;
+      const dim3 gs = grid_tstg(rh), bs(kBX, kTSY);
+      if (hb_done && vg)
+        hipLaunchKernelGGL((k_pre_tracer_stg<true, true>), gs, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+      else if (hb_done)
+        hipLaunchKernelGGL((k_pre_tracer_stg<true, false>), gs, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+      else if (vg)
+        hipLaunchKernelGGL((k_pre_tracer_stg<false, true>), gs, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+      else
+        hipLaunchKernelGGL((k_pre_tracer_stg<false, false>), gs, bs, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
+      t_hstg_launches(kTHstgPre, 1);
+      if (vg) t_hstg_launches(kTHstgHz, 1);
+    } else if (d.p.hoist && b.NT == 2 && hb_done)
       hipLaunchKernelGGL((k_pre_tracer_h1<2, true>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);
     else if (d.p.hoist && b.NT == 2)
       hipLaunchKernelGGL((k_pre_tracer_h1<2, false>), gh, bh, 0, s, d, rh, c, t.nstp, t.nnew, t.nrhs);

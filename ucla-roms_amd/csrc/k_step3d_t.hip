@@ -106,6 +106,74 @@ __global__ void __launch_bounds__(kBX * kBY) k_step3d_t_h1(Dev d, Range R, int n
   }
 }
 
+// The same for two tracers as one block per tile walking the levels
+// (Params::t_hstg bit kTHstgCor; TracerStg, k_common.h): the lane's masks, pm,
+// pn and the river tests once per block instead of once per level, each
+// level's FlxU, FlxV, T, S windows in flight a level ahead, the lane's stencil
+// read from them once for its four faces (tracer_stg_fluxes).  Lanes past the
+// range walk too (barriers) and store nothing.  Per level the expressions of
+// k_step3d_t_h1<2> in their order: bit-identical.
+__global__ void __launch_bounds__(kTSB, kTSWaves) k_step3d_t_stg(Dev d, Range R, int nnew, int nrhs) {
+  const uint3 bI = xcd_tile();
+  __shared__ TracerStg W;
+  const Bounds& b = d.b;
+  const Fields& F = d.f;
+  const int N = b.N;
+  const int i0 = tile_i0(R.i0) + (int)bI.x * kBX, j0 = R.j0 + (int)bI.y * kTSY;
+  const int ib = i0 - 2, jb = j0 - 2;
+  const long n2 = b.n2;
+  const int tid = threadIdx.x + kBX * threadIdx.y;
+  const TracerStgLd E(b, ib, jb, tid);
+  const long ts = 3 * b.n3;   // itemp -> isalt
+  const BufF64 FU(F.FlxU), FV(F.FlxV);
+  const BufF64 Tr0(F.t + (long)(nrhs - 1) * b.n3), Tr1(F.t + (long)(nrhs - 1) * b.n3 + ts);
+  const BufF64 Tn0(F.t + (long)(nnew - 1) * b.n3), Tn1(F.t + (long)(nnew - 1) * b.n3 + ts);
+  const unsigned ls = (unsigned)n2 * 8u;   // a level's bytes
+  double w[4][kTSR];
+  E.ld(FU, FV, Tr0, Tr1, 0u, w);
+  const int i = i0 + (int)threadIdx.x, j = j0 + (int)threadIdx.y;
+  const bool act = i >= R.i0 && i <= R.i1 && j <= R.j1;
+  const long ij = act ? IJ(b, i, j) : IJ(b, R.i0, R.j0);
+  const unsigned vo = (unsigned)ij * 8u, vs = act ? vo : kBufOff;   // lanes past the range store nothing
+  const double pm = F.pm[ij], pn = F.pn[ij];
+  const TracerStgMask M(b, F, ij);
+  // river inflow faces of the lane's cell (river_tracer_flux's own test, once)
+  bool rx0 = false, rx1 = false, re0 = false, re1 = false;
+  if (d.p.nriv > 0 && act) {
+    rx0 = fabs(F.riv_uflx[ij]) > 1e-3; rx1 = fabs(F.riv_uflx[ij + 1]) > 1e-3;
+    re0 = fabs(F.riv_vflx[ij]) > 1e-3; re1 = fabs(F.riv_vflx[ij + b.nx2]) > 1e-3;
+  }
+  const bool riv = rx0 || rx1 || re0 || re1;
+  const int cw = (int)threadIdx.x + 2 + ((int)threadIdx.y + 2) * kUVW;   // the lane's cell in the windows
+  unsigned lev = 0u;   // (k-1)*n2*8
+  for (int k = 1; k <= N; k++, lev += ls) {
+    // the lane's t(nnew) of this level: lands under the barriers and the fluxes
+    // (held a level ahead it needs a second register set and a copy per level,
+    // which waits for every load in flight)
+    const double tn0 = Tn0.ld(vo, lev), tn1 = Tn1.ld(vo, lev);
+    if (k > 1) __syncthreads();   // the previous level's windows consumed
+    W.put(tid, w);
+    if (k < N) E.ld(FU, FV, Tr0, Tr1, lev + ls, w);
+    __syncthreads();
+    const TracerStgFlx S(W, cw);
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+      const int itrc = t + 1;
+      double FX0, FX1, FE0, FE1;   // act lanes lie in istr..iend x jstr..jend (tracer_stg_fluxes' precondition); the others store nothing
+      tracer_stg_fluxes(b, W, M, S, t, cw, i, j, true, FX0, FX1, FE0, FE1);
+      if (riv) {   // river inflow faces (compute_horiz_tracer_fluxes.h:217-246)
+        int kr = k, ir = i, jr = j;   // opaque: the faces' addresses are formed here, not carried up the levels by every lane
+        __asm__ volatile("" : "+s"(kr), "+v"(ir), "+v"(jr));
+        if (rx0) river_tracer_flux(d, 0, ir, jr, kr, itrc, FX0);
+        if (rx1) river_tracer_flux(d, 0, ir + 1, jr, kr, itrc, FX1);
+        if (re0) river_tracer_flux(d, 1, ir, jr, kr, itrc, FE0);
+        if (re1) river_tracer_flux(d, 1, ir, jr + 1, kr, itrc, FE1);
+      }
+      (t == 0 ? Tn0 : Tn1).st((t == 0 ? tn0 : tn1) - d.p.dt * pm * pn * (FX1 - FX0 + FE1 - FE0), vs, lev);
+    }
+  }
+}
+
 // Vertical part per column: spline advection on t(nrhs), surface fluxes
 // (+ KPP non-local and solar terms), implicit diffusion.  LDS slots: A holds
 // FC (spline) then DC(k) at A[k-1]; B holds the spline CF then Thomas CF.
@@ -751,7 +819,10 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
   // horizontal fluxes, then the column solves, on a sub-range of the interior
   auto h_tiles = [&](const Range& r) {
     const dim3 gh = grid3_of(r, b.N), bh(kBX, kBY);
-    if (d.p.hoist && b.NT == 2)
+    if (d.p.hoist && b.NT == 2 && (d.p.t_hstg & kTHstgCor)) {
+      hipLaunchKernelGGL(k_step3d_t_stg, grid_tstg(r), dim3(kBX, kTSY), 0, s, d, r, t.nnew, t.nrhs);
+      t_hstg_launches(kTHstgCor, 1);
+    } else if (d.p.hoist && b.NT == 2)
       hipLaunchKernelGGL(k_step3d_t_h1<2>, gh, bh, 0, s, d, r, t.nnew, t.nrhs);
     else if (d.p.hoist && b.NT == 1)
       hipLaunchKernelGGL(k_step3d_t_h1<1>, gh, bh, 0, s, d, r, t.nnew, t.nrhs);

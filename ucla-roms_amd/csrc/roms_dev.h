@@ -98,7 +98,11 @@ struct Params {
   // (ROMS_GPU_T_PAIR bits: 1 k_pre_tracer_segb_pair, 2 k_step3d_t_segb_pair).  The bits in force: the configured mask while Akt(isalt) is
   // Akt(itemp) bit for bit (the shim's akt_same flag, set by lmd_vmix, cleared by a host write of Akt), else 0.
   int t_pair;
-  int reserved_[6];
+  // t_hstg took the third: the horizontal tracer kernels of pre_step3d / step3d_t (two tracers) as one block per
+  // 64x8 cells walking the levels over staged windows (ROMS_GPU_T_HSTG bits: 1 k_pre_tracer_stg, 2 k_step3d_t_stg,
+  // 4 k_pre_tracer_stg forms Hz from VGrid).  The bits in force: bit 4 only while the grid's validity flag holds.
+  int t_hstg;
+  int reserved_[5];
   // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
@@ -243,6 +247,9 @@ constexpr int kVg2Default = kVg2All;  // profiles/r10_vgrid_rest_ab.txt
 // Params::t_pair bits (ROMS_GPU_T_PAIR)
 constexpr int kTPairPre = 1, kTPairCor = 2, kTPairAll = 3;
 constexpr int kTPairDefault = kTPairAll;
+// Params::t_hstg bits (ROMS_GPU_T_HSTG)
+constexpr int kTHstgPre = 1, kTHstgCor = 2, kTHstgHz = 4, kTHstgAll = 7;
+constexpr int kTHstgDefault = kTHstgAll, kTHstgDefaultCol = kTHstgCor;   // segment path / column solvers (profiles/r13_tracer_stg_ab.txt)
 struct VGrid {
   const double *Cs_w, *Cs_r;
   double z, h, hinv, hc, ds;
@@ -502,6 +509,10 @@ int s2d_edge_modes_taken(bool reset = false);
 // per Params::t_pair bit (kTPairPre or kTPairCor; add: count `add` launches
 // of `bit`); a replayed graph counts the launches of its capture only
 long t_pair_launches(int bit, long add = 0, bool reset = false);
+// the same for the staged horizontal tracer kernels, per Params::t_hstg bit
+// (kTHstgPre: k_pre_tracer_stg, kTHstgCor: k_step3d_t_stg, kTHstgHz: the
+// k_pre_tracer_stg launches among them that formed Hz)
+long t_hstg_launches(int bit, long add = 0, bool reset = false);
 bool prsgrd_takes_strips(const Dev& d, bool with_uv, int& jA, int& jB, int& nstrip);
 double pre_step3d_dtau(const Dev& d, const Tlev& t);   // pre_step3d's dtau (k_pre_step3d.hip)
 void launch_rho_eos(const Dev& d, hipStream_t s, const Tlev& t, int tidx);

@@ -76,6 +76,7 @@ struct Ctx {
   // Params::t_pair carry T and S over one matrix (akt_set).
   bool akt_same = false;
   int t_pair_cfg = 0;   // ROMS_GPU_T_PAIR as read at init
+  int t_hstg_cfg = 0;   // ROMS_GPU_T_HSTG as read at init; Params::t_hstg drops bit kTHstgHz while !vgrid_valid
   std::string err;
   // graph cache: key = (nstp, knew at step start)
   std::map<long, hipGraphExec_t> graphs;
@@ -154,6 +155,7 @@ void drop_graphs() {   // captured graphs hold the old Params / pointers
 void vg_set(bool valid) {
   g.vgrid_valid = valid;
   g.d.p.vg = valid ? (short)(g.d.p.vgrid | (g.d.p.vgrid2 << kVg2Shift)) : (short)0;
+  g.d.p.t_hstg = valid ? g.t_hstg_cfg : (g.t_hstg_cfg & ~kTHstgHz);
 }
 void akt_set(bool same) {
   g.akt_same = same;
@@ -913,6 +915,16 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   P.t_pair = 0;
   g.akt_same = false;
   (void)t_pair_launches(0, 0, true);
+  // the horizontal tracer kernels as one block per tile walking the levels
+  // over staged windows (bits in roms_dev.h; bit 4, Hz formed in the
+  // predictor, in force under the grid's validity flag and with bit 1 only);
+  // ROMS_GPU_T_HSTG=0 for the per-level k_*_h1 kernels.  Default: all on the
+  // segment path (C3: every part below the parent in its routine); with the
+  // column solvers (C2, N = 50) the corrector only, the predictor's walk
+  // measured 0.02 ms above the per-level kernel there (profiles/r13_tracer_stg_ab.txt)
+  g.t_hstg_cfg = env_int("ROMS_GPU_T_HSTG", P.colseg ? kTHstgDefault : kTHstgDefaultCol, 0, kTHstgAll);
+  P.t_hstg = g.t_hstg_cfg & ~kTHstgHz;
+  (void)t_hstg_launches(0, 0, true);
   P.hoist = !env_off("ROMS_GPU_HOIST");
   // default on: C3 prsgrd 3.62-3.63 -> 3.55 ms per call (r5_d_seg_buf_chunk_prs_ab.txt)
   P.prs_buf = !env_off("ROMS_GPU_PRS_BUF");
@@ -1201,6 +1213,16 @@ int roms_gpu_tracer_pair(long launches[2]) {
   REQUIRE_INIT_NOJOIN();
   if (launches) { launches[0] = t_pair_launches(kTPairPre); launches[1] = t_pair_launches(kTPairCor); }
   return g.t_pair_cfg + (g.akt_same ? 256 : 0);
+}
+
+int roms_gpu_tracer_hstg(long launches[3]) {
+  REQUIRE_INIT_NOJOIN();
+  if (launches) {
+    launches[0] = t_hstg_launches(kTHstgPre);
+    launches[1] = t_hstg_launches(kTHstgCor);
+    launches[2] = t_hstg_launches(kTHstgHz);
+  }
+  return g.t_hstg_cfg + (g.vgrid_valid ? 256 : 0);
 }
 
 int roms_gpu_vgrid_check(long out[3]) {

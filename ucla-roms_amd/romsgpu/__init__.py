@@ -579,6 +579,18 @@ class Model:
         self._chk(min(r, 0), "tracer_pair")
         return r % 256, bool(r // 256), (n[0], n[1])
 
+    def tracer_hstg(self):
+        """(mask, valid, (pre, cor, pre_hz)): the horizontal tracer kernels
+        that walk the levels over staged windows (ROMS_GPU_T_HSTG, as read at
+        init: 1 pre_step3d, 2 step3d_t, 4 Hz formed in pre_step3d), whether
+        the grid is valid so that bit 4 is in force, and the launches of
+        k_pre_tracer_stg, of k_step3d_t_stg and of the k_pre_tracer_stg that
+        formed Hz enqueued since init (roms_gpu_tracer_hstg)."""
+        n = (ctypes.c_long * 3)(0, 0, 0)
+        r = self.L.roms_gpu_tracer_hstg(n)
+        self._chk(min(r, 0), "tracer_hstg")
+        return r % 256, bool(r // 256), (n[0], n[1], n[2])
+
     def vgrid_mismatch(self):
         """(z_w, z_r, Hz): stored values that differ bitwise from the ones
         formed from the kept free surface, h and hinv, over set_depth's range
