@@ -268,8 +268,10 @@ void or_rho_eos(or_state *S, int tidx) {
       for (int k = 1; k <= N; k++)
         for (int i = S->istrE; i <= S->iendE; i++) {
           Tt = TT(i, j, k, tidx, 1);
-          Ts = TT(i, j, k, tidx, 2);
-          sqrtTs = sqrt(dmax(0.0, Ts));
+          if (S->c.salinity) {  /* rho_eos.F:213-215: without SALINITY Ts stays 34.5 */
+            Ts = TT(i, j, k, tidx, 2);
+            sqrtTs = sqrt(dmax(0.0, Ts));
+          }
           const double rm = A2(S->rmask, i, j);
           R3(S->rho1, i, j, k) =
               (dr00 + Tt * (r01 + Tt * (r02 + Tt * (r03 + Tt * (r04 + Tt * r05)))) +

@@ -1,0 +1,297 @@
+"""States that take the data-dependent branches of the hot path.
+
+The per-routine GPU tests feed the kernels mid-run states of the analytic
+cases; on those states several branches that depend on the data run in one
+arm only ("Branch coverage").  Each builder below makes,
+from the CPU oracle alone, a state whose data reach the other arms, and
+returns (cfg, oracle, time indices) with the indices already set in the
+oracle.  Beside each builder stands a short numpy restatement of the branch
+condition from the routine's inputs, which tests/test_branch_states.py uses
+to assert what share of the points runs each arm (and, where the restatement
+also yields the output, to check the oracle's own lines a second time).
+tests/test_gpu_branches.py runs the HIP kernels on the same states.
+
+  omega_state    omega.F's Courant split: cw < cw_min, cw < cutoff*cw_max, the
+                 rest, and cw_max <= 0 (We = 0), reached by scaling the
+                 horizontal fluxes column by column over 4.5 decades
+  drag_state     linear bottom drag (Zob = 0) with rdrg inside the range of
+                 the 0.8*Hz/dt clamp
+  flather_state  Flather's correction for cx > 1 - 1/sqrt(2): a mid-run
+                 state of the open basin handed to a model with ndtfast = 4
+                 (whole runs at that ndtfast blow up), on 2.3 km curvilinear
+                 cells so that every edge has points on both sides
+  cext_state     boundary data of both signs on every side of u3dbc / v3dbc
+  kpp_eos_state  KPP over the linear EOS, and over the split EOS without
+                 salinity
+  kpp_top_state  surface heating and weak wind: the boundary layer ends
+                 inside the top cell
+  kpp_swr_state  well-mixed columns under cooling and wind: the boundary
+                 layer reaches levels where swr_frac is exactly zero
+"""
+import numpy as np
+
+import oracle
+import romsgpu
+from test_gpu_obc import obc_cfg
+from test_gpu_parity import basin_cfg
+
+G = 9.81
+K_FL = 0.292893218813452      # u2dbc_im.F:36, 1 - 1/sqrt(2)
+FLUX_DECADES = 4.5            # omega_state: 10**(FLUX_DECADES*rand) per column
+
+
+def _started(cfg, steps=3):
+    o = oracle.Oracle(cfg)
+    o.init()
+    o.step(steps)
+    return o
+
+
+def set_mode(o, mode):
+    """Predictor (nrhs = nstp, nnew = 3) or corrector (nrhs = 3, nnew = 3 - nstp) indices."""
+    iic, kstp, knew, nstp = o.tindex()[:4]
+    tix = [iic, kstp, knew, nstp, 3, 3 - nstp] if mode == "corr" else [iic, kstp, knew, nstp, nstp, 3]
+    o.set_tindex(tix)
+    return tix
+
+
+def box(cfg):
+    """Index of the interior points (1..Lm, 1..Mm) of a (.., Mm+4, Lm+4) array."""
+    return (Ellipsis, slice(2, cfg.MMm + 2), slice(2, cfg.LLm + 2))
+
+
+def kpp_cfg(LLm, MMm, N, nonlin=True, NT=2, salinity=1):
+    """The closed basin with KPP and surface fluxes on 2 km cells (the depth
+    and width sweeps' case)."""
+    c = basin_cfg(nonlin=nonlin, LLm=LLm, MMm=MMm, N=N, NT=NT, sizex=2.0e3 * LLm, sizey=2.0e3 * MMm)
+    c.salinity = salinity
+    c.lmd, c.surf_flux = oracle.LMD_ALL, 1
+    return c
+
+
+# ---------------------------------------------------------------- omega ----
+def omega_state(LLm, MMm, N, decades=FLUX_DECADES):
+    cfg = kpp_cfg(LLm, MMm, N)
+    o = _started(cfg)
+    rng = np.random.default_rng(5)
+    for name in ("FlxU", "FlxV"):
+        f = o.field(name)
+        f *= 10.0 ** (decades * rng.random(f.shape[1:]))[None] * (1.0 + 0.5 * rng.standard_normal(f.shape))
+    return cfg, o, set_mode(o, "pred")
+
+
+def omega_split(o, cfg, tix):
+    """omega.F:60-160 from FlxU, FlxV, Hz, z_w, swflx and the metrics, in the
+    reference's operation order: (We, Wi, regime) on the interior, regime
+    1..4 at the w-points k = 1..N-1 (0 at k = 0 and N)."""
+    N, I = cfg.N, box(cfg)
+    IX, JX = (Ellipsis, I[1], slice(3, cfg.LLm + 3)), (Ellipsis, slice(3, cfg.MMm + 3), I[2])
+    FU, FV, Hz, zw = o.field("FlxU"), o.field("FlxV"), o.field("Hz"), o.field("z_w")
+    dtau = cfg.dt if tix[4] == 3 else 0.6 * cfg.dt     # iic is past forw_start
+    pos, neg = lambda x: np.maximum(x, 0.0), lambda x: np.minimum(x, 0.0)
+    W, CX = np.zeros((N + 1,) + zw[0][I].shape), np.zeros((N + 2,) + zw[0][I].shape)
+    for k in range(1, N + 1):
+        W[k] = W[k - 1] - FU[k - 1][IX] + FU[k - 1][I] - FV[k - 1][JX] + FV[k - 1][I]
+        CX[k] = pos(FU[k - 1][IX]) - neg(FU[k - 1][I]) + pos(FV[k - 1][JX]) - neg(FV[k - 1][I])
+    W[N] = W[N] + o.field("swflx")[0][I] * o.field("dm_r")[0][I] * o.field("dn_r")[0][I]
+    wrk = W[N] / (zw[N][I] - zw[0][I])
+    cx0 = dtau * o.field("pm")[0][I] * o.field("pn")[0][I]
+    We, Wi, reg = np.zeros_like(W), np.zeros_like(W), np.zeros(W.shape, dtype=int)
+    for k in range(N - 1, 0, -1):
+        w = W[k] - wrk * (zw[k][I] - zw[0][I])
+        cw_max = 1.0 * np.minimum(Hz[k - 1][I], Hz[k][I]) - np.maximum(CX[k], CX[k + 1]) * cx0
+        cw, cw_min = np.abs(w) * cx0, cw_max * 0.6
+        r = np.where(cw_max <= 0.0, 4, np.where(cw < cw_min, 1, np.where(cw < 1.4 * cw_max, 2, 3)))
+        with np.errstate(all="ignore"):
+            cff = np.where(r == 1, cw_max * cw_max,
+                           np.where(r == 2, cw_max * cw_max + 0.625 * ((cw - cw_min) * (cw - cw_min)), cw_max * cw))
+            we = np.where(r == 4, 0.0, cw_max * cw_max * w / cff)
+        We[k], Wi[k], reg[k] = we, np.where(r == 4, w, w - we), r
+    return We, Wi, reg
+
+
+# ----------------------------------------------------------- linear drag ----
+RDRG = 2.5   # [m/s]; 0.8*Hz(k=1)/dt spans 0.35 .. 9.7 on this basin at dt = 60 s
+
+
+def drag_state():
+    cfg = basin_cfg(nonlin=True)
+    cfg.Zob, cfg.rdrg = 0.0, RDRG
+    o = _started(cfg)
+    return cfg, o, set_mode(o, "pred")
+
+
+def drag_clamp(o, cfg):
+    """compute_rd_bott_drag.h without Zob: (r_D, clamp binds) on the interior."""
+    lim = 0.8 * o.field("Hz")[0][box(cfg)] / cfg.dt
+    return np.minimum(cfg.rdrg, lim), lim < cfg.rdrg
+
+
+# --------------------------------------------------------------- Flather ----
+FLATHER_NDTFAST = 4
+FLATHER_CELL = 2.3e3
+
+
+def flather_cfg(obc, ndtfast=FLATHER_NDTFAST):
+    return obc_cfg(obc=obc, curv=1, ndtfast=ndtfast, sizex=FLATHER_CELL * 48, sizey=FLATHER_CELL * 40)
+
+
+def flather_state(obc):
+    """Three steps at ndtfast = 30, then every field handed to a model of the
+    same grid with ndtfast = 4: one state for single step2d calls, not a run.
+    The indices returned are those after the three steps; step2d's callers
+    advance kstp / knew themselves (fast_indices)."""
+    donor = _started(flather_cfg(obc, ndtfast=30))
+    cfg = flather_cfg(obc)
+    o = oracle.Oracle(cfg)
+    o.init()
+    for name in romsgpu.FIELDS:
+        o.field(name)[...] = donor.field(name)
+    tix = donor.tindex()
+    o.set_tindex(tix)
+    return cfg, o, tix
+
+
+def fast_indices(tix, iif):
+    """Indices of fast step iif = 1, 2, .. after the state's (step2d_FB.F's kstp / knew rotation)."""
+    iic, kstp, knew, nstp = tix[:4]
+    for _ in range(iif):
+        kstp, knew = knew, knew % 4 + 1
+    return [iic, kstp, knew, nstp, 3, 3 - nstp]
+
+
+def flather_cx(o, cfg):
+    """cx of u2dbc / v2dbc (u2dbc_im.F:31-34) along each open side."""
+    L, M = cfg.LLm, cfg.MMm
+    h, pm, pn = o.field("h")[0], o.field("pm")[0], o.field("pn")[0]
+    dtf = cfg.dt / cfg.ndtfast
+
+    def cx(a, b, p):
+        cff = 0.5 * (h[a] + h[b])
+        return dtf * cff * np.sqrt(G / cff) * 0.5 * (p[a] + p[b])
+
+    js, is_ = slice(2, M + 2), slice(2, L + 2)
+    sides = {"west": (1, cx((js, 1), (js, 2), pm)), "east": (2, cx((js, L + 1), (js, L + 2), pm)),
+             "south": (4, cx((1, is_), (2, is_), pn)), "north": (8, cx((M + 1, is_), (M + 2, is_), pn))}
+    return {s: c for s, (bit, c) in sides.items() if cfg.obc & bit}
+
+
+# ------------------------------------------------------------------ cext ----
+CEXT_FIELDS = {"west": "u_west", "east": "u_east", "south": "v_south", "north": "v_north"}
+
+
+def cext_state(mode):
+    """The open basin after three steps with a sign-changing wave added to the
+    normal-velocity boundary data of every side (amplitude twice the data's)."""
+    cfg = obc_cfg(obc=15)
+    o = _started(cfg)
+    for q, name in enumerate(CEXT_FIELDS.values()):
+        a = o.field(name).reshape(cfg.N, -1)
+        m, k = np.arange(a.shape[1])[None, :], np.arange(cfg.N)[:, None]
+        a += 2.0 * np.abs(a).max() * np.sin(2.0 * np.pi * 3.0 * m / a.shape[1] + 0.4 * k + q)
+    return cfg, o, set_mode(o, mode)
+
+
+def cext_arms(o, cfg, tix):
+    """Per side, over the edge's normal-velocity points: the shares whose
+    boundary data flow in / out (the test of u3dbc_im.F:96-97 and its three
+    twins), and the shares that ran either arm, i.e. where the Orlanski
+    inflow flag cx < 0 (u3dbc_im.F:80-92) was also set.  Call after the
+    routine: the flag needs the interior u, v (nnew) it has just formed."""
+    N, L, M = cfg.N, cfg.LLm, cfg.MMm
+    nstp, nnew = tix[3], tix[5]
+    lev = lambda a, l: a[(l - 1) * N:l * N]
+    u, v = o.field("u"), o.field("v")
+    js, is_ = slice(2, M + 2), slice(2, L + 2)
+    pick = {"west": (u, (js, 3), (js, 4), 1.0), "east": (u, (js, L + 1), (js, L), -1.0),
+            "south": (v, (3, is_), (4, is_), 1.0), "north": (v, (M + 1, is_), (M, is_), -1.0)}
+    out = {}
+    for side, (a, i1, i2, sgn) in pick.items():
+        i1, i2 = (Ellipsis,) + i1, (Ellipsis,) + i2
+        dft = lev(a, nstp)[i1] - lev(a, nnew)[i1]
+        dfx = lev(a, nnew)[i1] - lev(a, nnew)[i2]
+        inflow = dft * dfx < 0.0
+        data_in = sgn * o.field(CEXT_FIELDS[side]).reshape(N, -1)[:, 1:-1] > 0.0
+        out[side] = {"data in": data_in.mean(), "data out": (~data_in).mean(),
+                     "ran bry arm": (inflow & data_in).mean(), "ran ubind arm": (inflow & ~data_in).mean()}
+    return out
+
+
+# ------------------------------------------------------------------- KPP ----
+KPP_SIZE = (40, 16)
+
+
+def kpp_eos_state(eos, mode, N=12):
+    """eos 'linear': KPP over the linear EOS with T and S; 'nosalt': over the
+    split EOS with NT = 1 and no salinity."""
+    if eos == "linear":
+        cfg = kpp_cfg(*KPP_SIZE, N, nonlin=False)
+    else:
+        cfg = kpp_cfg(*KPP_SIZE, N, NT=1, salinity=0)
+    o = _started(cfg)
+    return cfg, o, set_mode(o, mode)
+
+
+def linear_bvf(o, cfg, tind):
+    """rho_eos.F's bvf over the linear EOS, k = 0..N, on the interior."""
+    N, I = cfg.N, box(cfg)
+    t, zr = o.field("t"), o.field("z_r")
+    T = t[(tind - 1) * N:tind * N][I]
+    rho = cfg.Tcoef * cfg.T0 - cfg.Tcoef * T
+    if cfg.salinity:
+        rho = (cfg.Tcoef * cfg.T0 - cfg.Scoef * cfg.S0) - cfg.Tcoef * T
+        rho = rho + cfg.Scoef * t[(3 + tind - 1) * N:(3 + tind) * N][I]
+    rho = rho * o.field("rmask")[0][I]
+    bvf = np.zeros((N + 1,) + rho.shape[1:])
+    bvf[1:N] = (G / cfg.rho0) * (rho[:-1] - rho[1:]) / (zr[1:][I] - zr[:-1][I])
+    bvf[N], bvf[0] = bvf[N - 1], bvf[1]
+    return bvf
+
+
+def _settle(o, tind, calls):
+    """lmd_vmix averages the new boundary-layer depths with the previous
+    ones (lmd_kpp.F:330-335): repeat it until they follow the forcing."""
+    for _ in range(calls):
+        o.L.or_lmd_vmix(o.h, tind)
+
+
+def kpp_top_state(N=12):
+    """Net surface heating (stflx > 0, a quarter of it short-wave) under a
+    tenth of the wind stress: the surface layer shoals into the top cell."""
+    cfg = kpp_cfg(*KPP_SIZE, N)
+    o = _started(cfg)
+    tix = set_mode(o, "pred")
+    o.field("srflx")[...] = 1.0e-4
+    o.field("stflx")[0][...] = 3.0e-4
+    o.field("sustr")[...] *= 0.1
+    _settle(o, tix[3], 6)
+    return cfg, o, tix
+
+
+def kpp_swr_state(N=12):
+    """Every column well mixed (T and S of the top level at all levels, bvf
+    from rho_eos), ten times the wind stress and ten times the cooling: the
+    surface layer deepens to the levels under a cell thicker than 460 m,
+    where lmd_swr_frac.F:60-75 has set both short-wave bands to exactly 0."""
+    cfg = kpp_cfg(*KPP_SIZE, N)
+    o = _started(cfg)
+    tix = set_mode(o, "pred")
+    t = o.field("t")
+    tv = t.reshape(cfg.NT, 3, N, t.shape[-2], t.shape[-1])
+    tv[...] = tv[:, :, N - 1:N]
+    o.L.or_rho_eos(o.h, tix[3])
+    o.field("stflx")[0][...] = -1.0e-3
+    o.field("sustr")[...] *= 10.0
+    _settle(o, tix[3], 8)
+    return cfg, o, tix
+
+
+def kpp_base(o, cfg):
+    """From the depths lmd_vmix left: kbls of lmd_kpp.F:348-352 per interior
+    column (N: the layer ends inside the top cell) and swr_frac(kbls-1)."""
+    N, I = cfg.N, box(cfg)
+    zw, hbl, sw = o.field("z_w"), o.field("hbls")[0][I], o.field("swr_frac")
+    kbls = np.full(hbl.shape, N)
+    for k in range(N - 1, 0, -1):
+        kbls = np.where(zw[k][I] > zw[N][I] - hbl, k, kbls)
+    return kbls, np.take_along_axis(sw[I], (kbls - 1)[None], 0)[0]

@@ -973,8 +973,11 @@ __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Ran
   // the next levels issue ahead of this level's stores
   // buffer accesses: the column in one VGPR offset, the level in an SGPR
   const unsigned vo = (unsigned)ij * 8u, lv = (unsigned)n2 * 8u;
-  const BufF64 T(F.t + (long)(tidx - 1) * b.n3), Sa(F.t + (long)(tidx - 1) * b.n3 + 3 * b.n3), zr(F.z_r), Hz(F.Hz),
-      rho1(F.rho1), qp1(F.qp1), bvf(F.bvf);
+  // without SALINITY there is no salt slot behind T (NT may be 1) and Ts keeps
+  // its 34.5 (rho_eos.F:198, 213-215): Sa then views T itself, its loads unused
+  const bool salt = P.salinity;
+  const BufF64 T(F.t + (long)(tidx - 1) * b.n3), Sa(F.t + (long)(tidx - 1) * b.n3 + (salt ? 3 * b.n3 : 0)), zr(F.z_r),
+      Hz(F.Hz), rho1(F.rho1), qp1(F.qp1), bvf(F.bvf);
   const bool lmd = P.lmd;
   const double gr = P.g / rho0;
   double r1p = 0.0, q1p = 0.0, zrp = 0.0;  // level k+1
@@ -1004,7 +1007,7 @@ __global__ void __launch_bounds__(256, ROMS_RHO_MINW) k_rho_eos_split(Dev d, Ran
   for (int k = N; k >= 1; k--) {
     const unsigned o = (unsigned)(k - 1) * lv;
     Tt = pT[0];
-    Ts = pS[0];
+    Ts = salt ? pS[0] : 34.5;
     double zrk, hz;
     if constexpr (VG) {
       const double cw = cw_n, cr = cr_n;
