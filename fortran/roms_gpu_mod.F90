@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 23  ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 24 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -136,6 +136,10 @@ module roms_gpu_mod
     integer(c_int) function roms_gpu_tracer_hstg(launches) bind(c)
       import :: c_int, c_long
       integer(c_long), intent(out) :: launches(3)
+    end function
+    ! ROMS_GPU_KPP_PF: levels of k_kpp_ext's sweep in flight ahead of the one formed
+    integer(c_int) function roms_gpu_kpp_pf() bind(c)
+      import :: c_int
     end function
     ! hot-path routines (one per reference subroutine)
     integer(c_int) function roms_gpu_rho_eos(tidx, t) bind(c)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 23
+#define ROMS_GPU_ABI_VERSION 24
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -321,6 +321,13 @@ int roms_gpu_column_path(void);
  *   4  k_kpp_int's kbls scan stops at the first level outside the layer.
  * Returns mask + 256 * keep of the live model, negative before init.       */
 int roms_gpu_kpp_lean(void);
+/* Levels in flight in k_kpp_ext's descending sweep (ABI 24).  The sweep loads
+ * the inputs of ROMS_GPU_KPP_PF levels (read at init, 1..4, default 3) ahead
+ * of the level it forms; 1 is the single level ahead at three waves per SIMD,
+ * 2..4 run at two.  A value outside 1..4 counts as 1.  Same values, same
+ * expressions: every field keeps its bits.  Returns the value of the live
+ * model, negative before init.                                              */
+int roms_gpu_kpp_pf(void);
 /* Hz, z_r, z_w formed inside the kernels.  The three arrays are functions of
  * the free surface set_depth used, h, hinv and the Cs tables; the kernels of
  * ROMS_GPU_VGRID (read at init; a mask, default 11, 0 for the streaming forms)

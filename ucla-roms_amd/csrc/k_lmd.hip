@@ -235,11 +235,22 @@ constexpr int kKppPfd = ROMS_KPP_PFD;
 #ifndef ROMS_KPP_EXT_WAVES
 #define ROMS_KPP_EXT_WAVES 3   // waves per SIMD the register budget is cut for (the next level in flight: 3)
 #endif
+//   PF     (Params::kpp_pf) levels of the descending sweep in flight ahead of
+//          the one formed: a ring of PF levels' loads, refilled with level
+//          k - PF at the top of level k, ahead of its Rig store and FC(k).
+//          1 is the single level ahead.  A level is 6 doubles with VG (9
+//          without) and the single level ahead uses 165 of the 168 VGPRs of
+//          3 waves per SIMD, so a second level spills there (4 VGPRs to
+//          scratch): the rings of 2 and more are cut for 2 waves per SIMD,
+//          kpp_ext_waves(PF).  Same values, same expressions, bitwise.  C3:
+//          1.12 ms per launch with 1, 0.79 with 2, 3 or 4
+//          (profiles/r15_kpp_ring_prs_vg_ab.txt).
+constexpr int kpp_ext_waves(int pf) { return pf <= 1 ? ROMS_KPP_EXT_WAVES : 2; }
 //   VG     (Params::vg bit kVgKppExt) Hz, z_r, z_w of the column from VGrid
 //          (roms_dev.h) instead of the three streamed arrays; z_w(k) is
 //          carried down the levels.
-template <class C, bool KEEP = false, bool VG = false>
-__global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range E, int tind, int nstp, KppConst kc) {
+template <class C, bool KEEP = false, bool VG = false, int PF = 1>
+__global__ void __launch_bounds__(64, kpp_ext_waves(PF)) k_kpp_ext(Dev d, Range E, int tind, int nstp, KppConst kc) {
   ROMS_IJC_OR_RETURN(E)
   const Bounds& b = d.b;
   const Fields& F = d.f;
@@ -325,17 +336,29 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   };
   // a level's inputs: u, v (and the i+1 / j+1 neighbours), Hz, z_r at rho
   // level k, z_w at w level k, sw and bvf at w level k-1 (its w level k
-  // values are the level above's); the next level's are loaded before this
-  // level's stores, so a level costs one memory round trip, not three
+  // values are the level above's); the next PF levels' are loaded before this
+  // level's stores, so a level costs 1/PF of a memory round trip, not three
   // (need_sw false: the swr_frac load is dropped -- kBufOff reads 0 without
   // a memory access -- once no Vtsq will use it)
-  struct Lv { double u0, u1, v0, v1, hz, zr, zw, swm, bm; };
+  // (VG with PF > 1: Cs_w(k-1) and Cs_r(k) travel with the level too.  Read
+  // where z_w and z_r are formed they are vector loads behind the levels in
+  // flight, and waiting for them waits for all of those)
+  struct Lv0 { double u0, u1, v0, v1, hz, zr, zw, swm, bm; };
+  struct Lv1 : Lv0 { double cw, cr; };
+  constexpr bool kCs = VG && PF > 1;
+  using Lv = std::conditional_t<kCs, Lv1, Lv0>;
+  const BufF64 CsW(F.Cs_w), CsR(F.Cs_r);   // the table entry in the scalar offset, like the level
   auto ldlev = [&](int k, Lv& L, bool need_sw) {
     const unsigned o = (unsigned)(k - 1) * lv, ow = (unsigned)k * lv;
     L.u0 = U.ld(vo, o); L.u1 = U.ld(vx, o); L.v0 = V.ld(vo, o); L.v1 = V.ld(vy, o);
     if constexpr (!VG) { L.hz = Hz.ld(vo, o); L.zr = zr.ld(vo, o); L.zw = zw.ld(vo, ow); }   // VG: formed at the level itself
+    if constexpr (kCs) { L.cw = CsW.ld(0u, (unsigned)(k - 1) * 8u); L.cr = CsR.ld(0u, (unsigned)k * 8u); }
     L.swm = sw.ld(need_sw ? vo : kBufOff, o); L.bm = bvf.ld(vo, o);
   };
+  // the level a slot takes, clamped at 1 (readfirstlane: the clamp is formed
+  // as a saturating subtraction in a VGPR otherwise, and every load of the
+  // level then loops over the lanes for its scalar offset)
+  auto ring_level = [](int k) { return __builtin_amdgcn_readfirstlane(k >= 1 ? k : 1); };
   // one level's term of the bulk Richardson integral (lmd_kpp.F:200-215):
   // u, v, Hz at rho levels k+1 (p) and k, z_w and bvf at w level k
   auto fc_term = [&](double u0p, double u1p, double v0p, double v1p, double hzp, double u0, double u1, double v0,
@@ -354,8 +377,15 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   double v0p = V.ld(vo, oN), v1p = V.ld(vy, oN);
   double hzp = VG ? zwN - zwc : Hz.ld(vo, oN), zrp = VG ? vg.zr(N) : zr.ld(vo, oN);
   double swc = sw.ld(vo, oN), bc = bvf.ld(vo, oN);   // sw, bvf at w level k (carried down)
-  Lv cur{};
-  if (N - 1 >= 1) ldlev(N - 1, cur, true);
+  Lv cur{};           // PF == 1: the level the sweep forms next
+  Lv S[PF + 2] = {};  // PF > 1: slots of the levels in flight (below)
+  if constexpr (PF == 1) {
+    if (N - 1 >= 1) ldlev(N - 1, cur, true);
+  } else {
+    S[0].u0 = u0p; S[0].u1 = u1p; S[0].v0 = v0p; S[0].v1 = v1p; S[0].swm = swc; S[0].bm = bc;   // level N
+#pragma unroll
+    for (int q = 1; q <= PF; q++) ldlev(ring_level(N - q), S[q], true);   // (clamped like the refills below)
+  }
   double FCk = 0.;
   fc_set(N, 0.);
   double Crp = FCk + vtsq(zrp, sw.ld(vo, (unsigned)N * lv), swc, bc);
@@ -363,23 +393,30 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
   double cr_k = Crp, cr_kp = 0., zr_k = zrp, zr_kp = 0.;
   // wave-uniform (lanes past the range have returned): every lane has its
   // kbls, so Vtsq, Cr and the swr_frac loads below are dropped.  The loads
-  // run one level ahead: the flag is settled before the next level's go out.
+  // run PF levels ahead: level k - PF goes out at the top of level k, where
+  // the flag holds what levels N .. k+1 settled.  The flag never clears, so
+  // a level issued without swr_frac is never asked for it, and a wave issues
+  // at most PF - 1 swr_frac loads (levels k-1 .. k-PF+1 when the flag sets at
+  // level k) that no Vtsq uses; the values used and their order are the same.
   const bool skipv = (P.kpp_lean & 1) != 0;
   bool vdone = skipv && __all(kbls != 0);
-  for (int k = N - 1; k >= 1; k--) {
-    Lv nxt = cur;
-    if (k > 1) ldlev(k - 1, nxt, !vdone);
+  // level k of the sweep from its inputs cur, the level above's u and v (p)
+  // and sw, bvf at w level k (the level above's swm, bm)
+  auto level = [&](int k, const Lv& cur, double u0p, double u1p, double v0p, double v1p, double swk, double bk) {
     const unsigned ow = (unsigned)k * lv;
     const double u0 = cur.u0, u1 = cur.u1, v0 = cur.v0, v1 = cur.v1;
     double hz, zrk, zwk;
-    if constexpr (VG) {
+    if constexpr (kCs) {
+      const double lo = vg.zw(k - 1, cur.cw);
+      zwk = zwc; zrk = vg.zr(k, cur.cr); hz = zwc - lo;
+      zwc = lo;
+    } else if constexpr (VG) {
       const double lo = vg_zw(vg, k - 1);
       zwk = zwc; zrk = vg.zr(k); hz = zwc - lo;
       zwc = lo;
     } else {
       hz = cur.hz; zrk = cur.zr; zwk = cur.zw;
     }
-    const double bk = bc;
     // raw gradient Richardson number (lmd_vmix.F:157-165), LMD_RIMIX only
     if (P.lmd_rimix) {
       const double cff = 0.5 / (zrp - zrk);
@@ -391,18 +428,52 @@ __global__ void __launch_bounds__(64, ROMS_KPP_EXT_WAVES) k_kpp_ext(Dev d, Range
     FCk = FCk + fc_term(u0p, u1p, v0p, v1p, hzp, u0, u1, v0, v1, hz, zwk, bk);
     fc_set(k, FCk);
     if (!vdone) {
-      const double Cr = FCk + vtsq(zrk, swc, cur.swm, cur.bm);
+      const double Cr = FCk + vtsq(zrk, swk, cur.swm, cur.bm);
       if (kbls == 0 && Cr < 0.) {
         kbls = k;
         cr_k = Cr; cr_kp = Crp; zr_k = zrk; zr_kp = zrp;
       }
       Crp = Cr;
-      swc = cur.swm;
+      if constexpr (PF == 1) swc = cur.swm;   // (the slots of PF > 1 keep it)
       vdone = skipv && __all(kbls != 0);
     }
-    u0p = u0; u1p = u1; v0p = v0; v1p = v1; hzp = hz; zrp = zrk;
-    bc = cur.bm;
-    cur = nxt;
+    hzp = hz; zrp = zrk;
+  };
+  if constexpr (PF == 1) {
+    for (int k = N - 1; k >= 1; k--) {
+      Lv nxt = cur;
+      if (k > 1) ldlev(k - 1, nxt, !vdone);
+      level(k, cur, u0p, u1p, v0p, v1p, swc, bc);
+      u0p = cur.u0; u1p = cur.u1; v0p = cur.v0; v1p = cur.v1;
+      bc = cur.bm;
+      cur = nxt;
+    }
+  } else {
+    // Level k sits in slot (N - k) mod M of M = PF + 2: at the top of level k
+    // the slots hold levels k+1 (its u, v, swm, bm are this level's p, sw, bvf)
+    // and k .. k-PF+1, and the slot of level k+2, read no more, takes level
+    // k - PF.  The sweep is unrolled by M so that every slot is a fixed set of
+    // registers: a ring shifted by register copies would have to wait for the
+    // loads in flight into the registers it copies.  The refill is clamped at
+    // level 1, not skipped: a reload of level 1 that nobody reads is harmless,
+    // while loads under a branch leave the compiler no count of the loads in
+    // flight at the join, and it then waits for all of them (vmcnt(0)) at
+    // every level.
+    constexpr int M = PF + 2;
+#pragma unroll 1
+    for (int kg = N - 1; kg >= 1; kg -= M) {
+#pragma unroll
+      for (int q = 0; q < M; q++) {
+        const int k = kg - q;
+        if (k >= 1) {
+          const Lv& prv = S[q];
+          const Lv& cur = S[(q + 1) % M];
+          ldlev(ring_level(k - PF), S[(q + M - 1) % M], !vdone);
+          level(k, cur, prv.u0, prv.u1, prv.v0, prv.v1, prv.swm, prv.bm);
+          if (k == 1) { u0p = cur.u0; u1p = cur.u1; v0p = cur.v0; v1p = cur.v1; }
+        }
+      }
+    }
   }
   // FC(0) (lmd_kpp.F:216-229): level-1 values are the carried ones, FCk is FC(1)
   double fc0;
@@ -795,10 +866,21 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
   kc.Vtc = Cv * std::sqrt(-betaT / (c_s * epssfc)) / (kRicr * (vonKar * vonKar));
   const int first = t.iic == t.forw_start;  // FIRST_TIME_STEP with EXACT_RESTART
   const bool vge = (d.p.vg & kVgKppExt) != 0, vgi = (d.p.vg & kVgKppInt) != 0;
-#define KPP_EXT(C, KEEP, lds)                                                                                       \
-  do {                                                                                                              \
-    if (vge) hipLaunchKernelGGL((k_kpp_ext<C, KEEP, true>), gridc_of(E), dim3(kCX), lds, s, d, E, tind, t.nstp, kc); \
-    else hipLaunchKernelGGL((k_kpp_ext<C, KEEP, false>), gridc_of(E), dim3(kCX), lds, s, d, E, tind, t.nstp, kc);   \
+#define KPP_EXT_PF(C, KEEP, VGF, PF, lds) \
+  hipLaunchKernelGGL((k_kpp_ext<C, KEEP, VGF, PF>), gridc_of(E), dim3(kCX), lds, s, d, E, tind, t.nstp, kc)
+#define KPP_EXT_VG(C, KEEP, VGF, lds)                     \
+  do {                                                    \
+    switch (d.p.kpp_pf) {   /* levels in flight */        \
+      case 2: KPP_EXT_PF(C, KEEP, VGF, 2, lds); break;    \
+      case 3: KPP_EXT_PF(C, KEEP, VGF, 3, lds); break;    \
+      case 4: KPP_EXT_PF(C, KEEP, VGF, 4, lds); break;    \
+      default: KPP_EXT_PF(C, KEEP, VGF, 1, lds); break;   \
+    }                                                     \
+  } while (0)
+#define KPP_EXT(C, KEEP, lds)                  \
+  do {                                         \
+    if (vge) KPP_EXT_VG(C, KEEP, true, lds);   \
+    else KPP_EXT_VG(C, KEEP, false, lds);      \
   } while (0)
   if (d.p.kpp_lean & 2)   // FC(0:keep) only, at every N
     KPP_EXT(ColLds, true, col_lds_bytes(1, d.p.kpp_fckeep < b.N ? d.p.kpp_fckeep : b.N));
@@ -807,6 +889,8 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
   else
     KPP_EXT(ColLds, false, col_lds_bytes(1, b.N));
 #undef KPP_EXT
+#undef KPP_EXT_VG
+#undef KPP_EXT_PF
 #define KPP_INT(DD, TY, MW, grid, block)                                                                              \
   do {                                                                                                                \
     if (vgi) hipLaunchKernelGGL((k_kpp_int<DD, TY, MW, true>), grid, block, 0, s, d, R, ec, tind, t.nstp, first, kc);  \

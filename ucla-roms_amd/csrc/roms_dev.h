@@ -102,7 +102,10 @@ struct Params {
   // 64x8 cells walking the levels over staged windows (ROMS_GPU_T_HSTG bits: 1 k_pre_tracer_stg, 2 k_step3d_t_stg,
   // 4 k_pre_tracer_stg forms Hz from VGrid).  The bits in force: bit 4 only while the grid's validity flag holds.
   int t_hstg;
-  int reserved_[5];
+  // kpp_pf took the fourth: levels of k_kpp_ext's descending sweep whose loads are in flight ahead of the level formed
+  // (ROMS_GPU_KPP_PF, 1..kKppPfMax; 1: the single level ahead; k_lmd.hip)
+  int kpp_pf;
+  int reserved_[4];
   // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
@@ -551,6 +554,8 @@ void launch_t3dbc(const Dev& d, hipStream_t s, const Tlev& t, int itrc);
 void launch_diag(const Dev& d, hipStream_t s, const Tlev& t, double* out);
 void launch_swr_frac(const Dev& d, hipStream_t s);
 constexpr int kKppFcKeepMax = 16;   // most levels above FC(0) in k_kpp_ext's LDS slot: 17 x 64 x 8 B = 8.7 KB per wave
+constexpr int kKppPfMax = 4;        // deepest ring of levels in flight k_kpp_ext is compiled for (Params::kpp_pf)
+constexpr int kKppPfDefault = 3;     // C3: k_kpp_ext 1.12 -> 0.79 ms per launch with 2, 3 or 4, profiles/r15_kpp_ring_prs_vg_ab.txt
 void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind);
 // ADV_ISONEUTRAL (k_iso.hip): prsgrd's corrector slopes (+ their exchange),
 // step3d_uv2's diff3u/diff3v/idRz over its flux-correction ranges and their

@@ -899,6 +899,13 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   // above FC(0) that k_kpp_ext keeps in LDS
   P.kpp_lean = (short)env_int("ROMS_GPU_KPP_LEAN", 7, 0, 7);
   P.kpp_fckeep = (short)env_int("ROMS_GPU_KPP_FCKEEP", kKppFcKeepMax, 1, kKppFcKeepMax);
+  // levels of k_kpp_ext's sweep in flight ahead of the one formed (bitwise);
+  // ROMS_GPU_KPP_PF=1 for the single level ahead, a value outside
+  // 1..kKppPfMax counts as 1
+  {
+    const int v = env_int("ROMS_GPU_KPP_PF", kKppPfDefault, -(1 << 30), 1 << 30);
+    P.kpp_pf = v >= 1 && v <= kKppPfMax ? v : 1;
+  }
   // Hz, z_r, z_w formed in the kernel from z_sd, h, hinv (VGrid, bitwise; the
   // bits in roms_dev.h); ROMS_GPU_VGRID=0 for the streaming forms, 1..15 a
   // set of kernels.  Default 11: k_kpp_int (bit 4) is slower with it
@@ -1241,6 +1248,11 @@ int roms_gpu_vgrid_check(long out[3]) {
 int roms_gpu_kpp_lean(void) {
   REQUIRE_INIT_NOJOIN();
   return g.d.p.kpp_lean + 256 * g.d.p.kpp_fckeep;
+}
+
+int roms_gpu_kpp_pf(void) {
+  REQUIRE_INIT_NOJOIN();
+  return g.d.p.kpp_pf;
 }
 
 int roms_gpu_horizontal_path(int out[8]) {

@@ -553,6 +553,14 @@ class Model:
         self._chk(min(r, 0), "kpp_lean")
         return r % 256, r // 256
 
+    def kpp_pf(self):
+        """Levels of k_kpp_ext's descending sweep whose loads are in flight
+        ahead of the level formed (ROMS_GPU_KPP_PF, as read at init; 1: the
+        single level ahead; roms_gpu_kpp_pf)."""
+        r = self.L.roms_gpu_kpp_pf()
+        self._chk(min(r, 0), "kpp_pf")
+        return r
+
     def vgrid(self):
         """(mask, valid): the kernels that form Hz, z_r, z_w themselves
         (ROMS_GPU_VGRID, as read at init) and whether the stored arrays are
