@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 24 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 25 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -265,6 +265,40 @@ module roms_gpu_mod
       integer(c_int), value :: rec, total_rec, wrt_mask
       real(c_double), value :: time
       type(roms_tlev), intent(in) :: t
+    end function
+    ! time-averaged output (k_avg.hip): calc_avg_ocean_vars / wrt_avg_ocean_vars
+    integer(c_int) function roms_gpu_avg_begin(wrt_mask) bind(c)
+      import :: c_int
+      integer(c_int), value :: wrt_mask
+    end function
+    integer(c_int) function roms_gpu_calc_avg(t, time) bind(c)
+      import :: c_int, c_double, roms_tlev
+      type(roms_tlev), intent(in) :: t
+      real(c_double), value :: time
+    end function
+    integer(c_int) function roms_gpu_wrt_avg(path, rec, total_rec, period, t) bind(c)
+      import :: c_int, c_double, c_char, roms_tlev
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: period
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_avg_state(navg, t_avg, mask) bind(c)
+      import :: c_int, c_double
+      integer(c_int), intent(out) :: navg, mask
+      real(c_double), intent(out) :: t_avg
+    end function
+    integer(c_int) function roms_gpu_avg_copy_out(wrt_bit, itrc, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: wrt_bit, itrc
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_time_calc_avg(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(in) :: t
+      real(c_double), intent(out) :: ms
     end function
     integer(c_int) function roms_gpu_io_wait() bind(c)
       import :: c_int

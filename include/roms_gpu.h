@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 24
+#define ROMS_GPU_ABI_VERSION 25
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -526,6 +526,49 @@ int roms_gpu_set_tides(double time);
 int roms_gpu_wrt_rst(const char *path, int rec, int total_rec, double time, const roms_tlev *t);
 int roms_gpu_wrt_his(const char *path, int rec, int total_rec, double time, const roms_tlev *t, int wrt_mask);
 int roms_gpu_io_wait(void);
+/* ---- time-averaged output on the device (ABI 25): calc_avg_ocean_vars
+ * (basic_output.F:1036-1118, tracers.F:252-269) and wrt_avg_ocean_vars
+ * (:421-515).  Averaging is off until roms_gpu_avg_begin arms it, and
+ * roms_gpu_step never samples by itself: the host owns `time`, so it calls
+ * roms_gpu_calc_avg after each step, as main.F:486 does.
+ * roms_gpu_avg_begin allocates one running mean per field of wrt_mask
+ * (ROMS_WRT_* bits; AKS without salinity and HBLS/HBBL without LMD are dropped
+ * silently, as roms_gpu_wrt_his drops them), each the size of one slot of its
+ * field, and sets navg = 0, t_avg = 0.  Mask 0 disarms and frees; calling it
+ * again re-arms from scratch; roms_gpu_finalize frees.
+ * roms_gpu_calc_avg takes one sample on the library stream (one kernel launch
+ * whatever the mask and NT): navg += 1, coef = 1/navg,
+ *   t_avg = t_avg*(1-coef) + time*coef,  X_avg = X_avg*(1-coef) + X*coef
+ * with X = zeta/ubar/vbar(t->knew), u/v/tracers(t->nstp), rho1 - qp1*z_r
+ * (SPLIT_EOS) or rho, We + Wi, Akv, Akt(itemp), Akt(isalt), hbls, hbbl.
+ * u, v and the tracers are sampled in slot nstp, NOT nnew: after a step nstp
+ * holds time n while zeta(knew) and `time` are at n+1 -- the reference's
+ * choice, kept for parity of the files.  The state at t = 0 is never sampled.
+ * At coef == 1 the old mean is not read.  Returns -4 when not armed.
+ * roms_gpu_wrt_avg writes record rec (rec 1 creates the file) through the
+ * writer of roms_gpu_wrt_his (device snapshot in stream order, ahead of the
+ * next sample; roms_gpu_io_wait joins it): ocean_time = t_avg, the history
+ * file's names, units and dimensions, 'averaged ' ahead of every long_name,
+ * type 'ROMS averages file', the global attribute averaging_timescale =
+ * '<period, one decimal> seconds', omega as (w_avg*pm)*pn.  Then navg = 0:
+ * the next sample starts a fresh window.  With no sample in the window (or
+ * not armed) it returns -4, writes nothing and resets nothing.
+ * roms_gpu_avg_state: a query (any pointer may be NULL).
+ * roms_gpu_avg_copy_out: the mean of ONE ROMS_WRT_* bit (itrc 1..NT for
+ * ROMS_WRT_T, ignored otherwise) in the host layout of its field, re-pitched
+ * as roms_gpu_copy_out does; count must be the field's one-slot size,
+ * (Lm+4)*(Mm+4) times 1, N or N+1.  Values outside the reference's write
+ * ranges (dimensions.F:40-45) are unspecified.
+ * roms_gpu_time_calc_avg: n samples between two events on the library stream,
+ * total milliseconds.  They go on from the open window (navg += n; after one
+ * roms_gpu_calc_avg every timed sample reads the old mean) and leave t_avg
+ * as it was: re-arm before the averages are used.                           */
+int roms_gpu_avg_begin(int wrt_mask);
+int roms_gpu_calc_avg(const roms_tlev *t, double time);
+int roms_gpu_wrt_avg(const char *path, int rec, int total_rec, double period, const roms_tlev *t);
+int roms_gpu_avg_state(int *navg, double *t_avg, int *mask);
+int roms_gpu_avg_copy_out(int wrt_bit, int itrc, double *dst, long count);
+int roms_gpu_time_calc_avg(int n, const roms_tlev *t, double *ms);
 /* t_vname/t_units/t_lname of tracer itrc (tracers.opt); default temp, salt, trcNN */
 int roms_gpu_io_tracer_name(int itrc, const char *name, const char *units, const char *long_name);
 /* Returns 0 (read), 1 (tindx 2: records not consecutive steps, nothing read),

@@ -397,6 +397,7 @@ hipError_t dev_alloc(double*& p, long n) {
 
 void free_all() {
   io_free();
+  avg_free();
   frc_free();
   if (g.small) { (void)hipFree(g.small); g.small = nullptr; g.small_n = 0; }
   if (g.stage) { (void)hipFree(g.stage); g.stage = nullptr; g.stage_n = 0; }
@@ -446,6 +447,7 @@ Tlev to_tlev(const roms_tlev* t) {
 // host <-> device layout copies (defined below)
 hipError_t field_h2d(int id, double* dev, const double* host);
 hipError_t rows_h2d(double* dev, const double* host, long rows);
+hipError_t rows_d2h(double* host, const double* dev, long rows);
 }  // namespace
 int roms::shim_enter(ShimState& S, bool read_only) {
   const int rho_keep = g.rho_slot;
@@ -459,6 +461,7 @@ double* roms::shim_field(int id) { return (id >= 0 && id < ROMS_NFIELDS) ? g.f[i
 long roms::shim_field_dev_count(int id) { return (id >= 0 && id < ROMS_NFIELDS) ? g.f[id].count : -1; }
 hipError_t roms::shim_field_h2d(int id, double* dev, const double* host) { return field_h2d(id, dev, host); }
 hipError_t roms::shim_rows_h2d(double* dev, const double* host, long rows) { return rows_h2d(dev, host, rows); }
+hipError_t roms::shim_rows_d2h(double* host, const double* dev, long rows) { return rows_d2h(host, dev, rows); }
 double* roms::shim_scratch_small(long n) {
   if (g.small_n < n) {
     if (g.small) { (void)hipStreamSynchronize(g.s); (void)hipFree(g.small); g.small = nullptr; }

@@ -14,7 +14,9 @@
 // joins the writer; a new write joins the previous one first (one staging
 // buffer).  Reads (get_init) are synchronous: host read, masking as the
 // reference does it, upload of packed slabs, one scatter kernel per variable,
-// and the reference's exchange_xxx after every field.
+// and the reference's exchange_xxx after every field.  Averages records
+// (wrt_avg_ocean_vars, basic_output.F:421-515) take the same write path with
+// the running means of k_avg.hip in place of the fields.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,7 +42,8 @@ struct Slab {
   long sj, sk;         // row and level strides
   int as_mask;         // riv_umask/riv_vmask: 1 where the river face array is non-zero
   // history omega (basic_output.F:374-384): pm*pn*(We+Wi) in m/s when src2
-  // (Wi) is set; pm/pn are 2-D, element (i0, j0)
+  // (Wi) is set; pm/pn are 2-D, element (i0, j0).  Averages omega
+  // (basic_output.F:482): src is w_avg, src2 unset, (w_avg*pm)*pn in that order
   const double* src2;
   const double *pm, *pn;
 };
@@ -54,6 +57,7 @@ __global__ void __launch_bounds__(256) k_io_pack(Slab s, double* __restrict__ ds
     const long o = i + j * s.sj;
     double v = s.src ? s.src[o + k * s.sk] : 0.0;
     if (s.src2) v = s.pm[o] * s.pn[o] * (v + s.src2[o + k * s.sk]);
+    else if (s.pm) v = v * s.pm[o] * s.pn[o];
     dst[q] = s.as_mask ? (v != 0.0 ? 1.0 : 0.0) : v;
   }
 }
@@ -193,8 +197,10 @@ void global_atts(nc::File& f, const ShimState& S, const char* type) {
   f.gatts.push_back(nc::Att::str("type", type));
 }
 
-// the variable list of a restart (def_vars_rst_ocean_vars) or history record
-std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst, int mask) {
+// the variable list of a restart (def_vars_rst_ocean_vars), history or, with
+// av, averages record (def_vars_ocean_vars(.true.): the running means of
+// k_avg.hip in place of the fields, 'averaged ' ahead of every long name)
+std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst, int mask, const AvgView* av = nullptr) {
   const Bounds& b = S.d->b;
   const Fields& F = S.d->f;
   const Part p = part_of(*S.dims);
@@ -202,26 +208,26 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   std::vector<OutVar> v;
   auto add = [&](const char* name, const char* ln, const char* un, char g, int lev, const double* base, long sk) {
     OutVar o;
-    o.name = name; o.lname = ln; o.units = un; o.grid = g; o.levels = lev;
+    o.name = name; o.lname = av ? std::string("averaged ") + ln : std::string(ln); o.units = un; o.grid = g; o.levels = lev;
     o.slab = slab_of(b, p, base, g, lev ? lev : 1, sk);
     v.push_back(o);
   };
   const long n2 = b.n2;
   const int knew = t.knew, nnew = t.nnew;
-  if (rst || (mask & ROMS_WRT_Z)) add("zeta", "free-surface elevation", "meter", 'r', 0, F.zeta + (knew - 1) * n2, 0);
+  if (rst || (mask & ROMS_WRT_Z)) add("zeta", "free-surface elevation", "meter", 'r', 0, av ? av->zeta : F.zeta + (knew - 1) * n2, 0);
   if (rst || (mask & ROMS_WRT_UB))
-    add("ubar", "vertically averaged u-momentum component", "meter second-1", 'u', 0, F.ubar + (knew - 1) * n2, 0);
+    add("ubar", "vertically averaged u-momentum component", "meter second-1", 'u', 0, av ? av->ubar : F.ubar + (knew - 1) * n2, 0);
   if (rst || (mask & ROMS_WRT_VB))
-    add("vbar", "vertically averaged v-momentum component", "meter second-1", 'v', 0, F.vbar + (knew - 1) * n2, 0);
-  if (rst || (mask & ROMS_WRT_U)) add("u", "u-momentum component", "meter second-1", 'u', N, F.u + (nnew - 1) * b.n3, n2);
-  if (rst || (mask & ROMS_WRT_V)) add("v", "v-momentum component", "meter second-1", 'v', N, F.v + (nnew - 1) * b.n3, n2);
+    add("vbar", "vertically averaged v-momentum component", "meter second-1", 'v', 0, av ? av->vbar : F.vbar + (knew - 1) * n2, 0);
+  if (rst || (mask & ROMS_WRT_U)) add("u", "u-momentum component", "meter second-1", 'u', N, av ? av->u : F.u + (nnew - 1) * b.n3, n2);
+  if (rst || (mask & ROMS_WRT_V)) add("v", "v-momentum component", "meter second-1", 'v', N, av ? av->v : F.v + (nnew - 1) * b.n3, n2);
   if (rst || (mask & ROMS_WRT_T)) {
     std::vector<std::string> nm, un, ln;
     tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
     for (int q = 0; q < b.NT; q++) {
       OutVar o;
-      o.name = nm[q]; o.lname = ln[q]; o.units = un[q]; o.grid = 'r'; o.levels = N;
-      o.slab = slab_of(b, p, F.t + (long)(nnew - 1) * b.n3 + (long)q * 3 * b.n3, 'r', N, n2);
+      o.name = nm[q]; o.lname = av ? "averaged " + ln[q] : ln[q]; o.units = un[q]; o.grid = 'r'; o.levels = N;
+      o.slab = slab_of(b, p, av ? av->t[q] : F.t + (long)(nnew - 1) * b.n3 + (long)q * 3 * b.n3, 'r', N, n2);
       v.push_back(o);
     }
   }
@@ -234,24 +240,24 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
     add("DV_avg_bak", "<back-step mixed fast-time-averaged vbar(:,:,n-1)>", "", 'v', 0, F.DV_avg_bak, 0);
   }
   if (!rst && (mask & ROMS_WRT_R)) {   // rho1 (SPLIT_EOS) or rho
-    add("rho", "density anomaly", "kilogram meter-3", 'r', N, S.cfg->nonlin_eos ? F.rho1 : F.rho, n2);
+    add("rho", "density anomaly", "kilogram meter-3", 'r', N, av ? av->rho : S.cfg->nonlin_eos ? F.rho1 : F.rho, n2);
   }
   if (!rst && (mask & ROMS_WRT_O)) {   // pm*pn*(We+Wi), m/s (basic_output.F:374-384)
-    add("omega", "S-coordinate vertical momentum component", "meter second-1", 'r', N + 1, F.We, n2);
+    add("omega", "S-coordinate vertical momentum component", "meter second-1", 'r', N + 1, av ? av->w : F.We, n2);
     Slab& o = v.back().slab;
-    const long off = o.src - F.We;   // element (i0, j0)
-    o.src2 = F.Wi + off;
+    const long off = o.src - (av ? av->w : F.We);   // element (i0, j0)
+    o.src2 = av ? nullptr : F.Wi + off;
     o.pm = F.pm + off;
     o.pn = F.pn + off;
   }
-  if (!rst && (mask & ROMS_WRT_AKV)) add("AKv", "vertical viscosity coefficient", "meter2 second-1", 'r', N + 1, F.Akv, n2);
+  if (!rst && (mask & ROMS_WRT_AKV)) add("AKv", "vertical viscosity coefficient", "meter2 second-1", 'r', N + 1, av ? av->akv : F.Akv, n2);
   if (!rst && (mask & ROMS_WRT_AKT))
-    add("AKt", "temperature vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, F.Akt, n2);
+    add("AKt", "temperature vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, av ? av->akt : F.Akt, n2);
   if (!rst && (mask & ROMS_WRT_AKS) && S.cfg->salinity)
-    add("AKs", "salinity vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, F.Akt + b.n3w, n2);
+    add("AKs", "salinity vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, av ? av->aks : F.Akt + b.n3w, n2);
   const bool kpp = S.cfg->lmd_mixing != 0;
-  if (kpp && (rst || (mask & ROMS_WRT_HBLS))) add("hbls", "Thickness of KPP surface boundary layer", "meter", 'r', 0, F.hbls, 0);
-  if (kpp && (rst || (mask & ROMS_WRT_HBBL))) add("hbbl", "Thickness of KPP bottom boundary layer", "meter", 'r', 0, F.hbbl, 0);
+  if (kpp && (rst || (mask & ROMS_WRT_HBLS))) add("hbls", "Thickness of KPP surface boundary layer", "meter", 'r', 0, av ? av->hbls : F.hbls, 0);
+  if (kpp && (rst || (mask & ROMS_WRT_HBBL))) add("hbbl", "Thickness of KPP bottom boundary layer", "meter", 'r', 0, av ? av->hbbl : F.hbbl, 0);
   if (rst) {
     add("riv_umask", "river mask at u points", "nondim", 'u', 0, F.riv_uflx, 0);
     v.back().slab.as_mask = 1;
@@ -261,14 +267,20 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   return v;
 }
 
-void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst) {
+void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst, bool avg = false,
+                 double period = 0.0) {
   const Part p = part_of(*S.dims);
   const int N = S.d->b.N;
   // create_file (roms_read_write.F:1161-1208): ocean_time first, then the global attributes
   const int dtm = f.add_dim("time", 0);
   f.add_var("ocean_time", nc::NC_DOUBLE, {dtm},
             {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
-  global_atts(f, S, rst ? "ROMS restart file" : "ROMS history file");
+  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : "ROMS history file");
+  if (avg) {   // the window length as F12.1, left-adjusted (basic_output.F:451-455, 705)
+    char tb[64];
+    snprintf(tb, sizeof tb, "%.1f seconds", period);
+    f.gatts.push_back(nc::Att::str("averaging_timescale", tb));
+  }
   const int daux = f.add_dim("auxil", 6);   // iaux
   f.add_var("time_step", nc::NC_INT, {dtm, daux},
             {nc::Att::str("long_name", "time step and record numbers from initialization")});
@@ -288,13 +300,22 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
   }
 }
 
-int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask) {
+int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask,
+                 bool avg = false, double period = 0.0) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
   if (!path || rec < 1 || !t) { *S.err = "roms_gpu_wrt: bad path/record/time levels"; return -1; }
+  const AvgView* av = nullptr;
+  if (avg) {   // wrt_avg_ocean_vars: the open window's means, ocean_time = their mean time
+    av = &avg_view();
+    if (!av->mask) { *S.err = "roms_gpu_wrt_avg: averaging is not armed (roms_gpu_avg_begin)"; return -4; }
+    if (av->navg == 0) { *S.err = "roms_gpu_wrt_avg: no sample in the window (roms_gpu_calc_avg)"; return -4; }
+    mask = av->mask;
+    time = av->t_avg;
+  }
   if ((r = io_join(*S.err))) return r;
-  std::vector<OutVar> vars = record_vars(S, *t, rst, mask);
+  std::vector<OutVar> vars = record_vars(S, *t, rst, mask, av);
   size_t n = 0;
   for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
   if (!io.drain) {
@@ -337,7 +358,8 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   const roms_tlev tl = *t;
   const bool create = rec == 1;
   nc::File* proto = new nc::File();
-  if (create) define_file(*proto, S, vars, rst);
+  if (create) define_file(*proto, S, vars, rst, avg, period);
+  if (avg) avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
   io.job.status = 0;
   io.job.err.clear();
   io.job.running = true;
@@ -384,6 +406,9 @@ int roms_gpu_wrt_rst(const char* path, int rec, int total_rec, double time, cons
 }
 int roms_gpu_wrt_his(const char* path, int rec, int total_rec, double time, const roms_tlev* t, int wrt_mask) {
   return write_record(path, rec, total_rec, time, t, false, wrt_mask);
+}
+int roms_gpu_wrt_avg(const char* path, int rec, int total_rec, double period, const roms_tlev* t) {
+  return write_record(path, rec, total_rec, 0.0, t, false, 0, true, period);
 }
 int roms_gpu_io_wait(void) {
   std::string err;

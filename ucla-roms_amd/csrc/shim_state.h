@@ -54,7 +54,22 @@ hipError_t shim_rows_h2d(double* dev, const double* host, long rows);   // `rows
 // row r = p*prow + q: dst[p*dplane + q*dpitch + c] = src[p*splane + q*spitch + c], c < width (device arrays; k_diag.hip)
 void launch_rows_copy(double* dst, long dpitch, long dplane, const double* src, long spitch, long splane, long width,
                       long rows, long prow, hipStream_t s);
-double* shim_scratch_small(long n);        // small device scratch owned by the context (>= n doubles)
+hipError_t shim_rows_d2h(double* host, const double* dev, long rows);   // the way back: device planes -> `rows` rows of Lm+4
+// Time-averaged output (k_avg.hip): the running means roms_gpu_calc_avg
+// maintains, each in the device layout of one slot of the field it mirrors
+// (nullptr: not selected), for rst_io.hip's averages-file writer.
+struct AvgView {
+  int mask = 0;        // ROMS_WRT_* bits armed (0: averaging off)
+  int navg = 0;        // samples in the open window
+  double t_avg = 0.0;  // their mean time
+  double *zeta = nullptr, *ubar = nullptr, *vbar = nullptr, *u = nullptr, *v = nullptr, *rho = nullptr, *w = nullptr,
+         *akv = nullptr, *akt = nullptr, *aks = nullptr, *hbls = nullptr, *hbbl = nullptr;
+  std::vector<double*> t;   // one per tracer
+};
+const AvgView& avg_view();
+void avg_window_written();   // wrt_avg: navg = 0, the next sample starts a fresh window
+void avg_free();             // roms_gpu_finalize
+double* shim_scratch_small(long n);      // small device scratch owned by the context (>= n doubles)
 // step3d_uv2's closed-edge column lists (k_step3d_uv.hip): (dir, i, j) triples
 void uv2_edge_lists(const Bounds& b, std::vector<int>& couple, std::vector<int>& flux);
 }  // namespace roms

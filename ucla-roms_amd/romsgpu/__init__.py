@@ -141,6 +141,12 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_wrt_his.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, P(Tlev), ctypes.c_int]
     L.roms_gpu_get_init.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     L.roms_gpu_io_tracer_name.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+    L.roms_gpu_avg_begin.argtypes = [ctypes.c_int]
+    L.roms_gpu_calc_avg.argtypes = [P(Tlev), ctypes.c_double]
+    L.roms_gpu_wrt_avg.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, P(Tlev)]
+    L.roms_gpu_avg_state.argtypes = [P(ctypes.c_int), P(ctypes.c_double), P(ctypes.c_int)]
+    L.roms_gpu_avg_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_time_calc_avg.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     _lib = L
     return L
 
@@ -203,6 +209,11 @@ HALO_DIRS = ("W", "E", "S", "N", "SW", "SE", "NW", "NE")
 # ROMS_WRT_* of include/roms_gpu.h (ocean_vars.opt wrt_* switches)
 WRT = dict(Z=1, Ub=2, Vb=4, U=8, V=16, T=32, R=64, O=128, Akv=256, Akt=512, Aks=1024, Hbls=2048, Hbbl=4096)
 WRT_DEFAULT = 63
+WRT_ALL = 8191
+# Model.avg names -> (ROMS_WRT_* bit, levels: 0 one plane, 1 N, 2 N+1)
+AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=(32, 1), temp=(32, 1), salt=(32, 1),
+                  rho=(64, 1), omega=(128, 2), Akv=(256, 2), Akt=(512, 2), Aks=(1024, 2), hbls=(2048, 0),
+                  hbbl=(4096, 0))
 # enum roms_routine of include/roms_gpu.h
 ROUTINES = ("rho_eos", "set_HUV", "omega", "prsgrd", "pre_step3d", "set_HUV1", "step3d_uv1", "visc3d", "step2d",
             "step3d_uv2", "step3d_t", "t3dmix", "lmd_vmix",
@@ -338,6 +349,7 @@ class Model:
             m._chk(m.L.roms_gpu_init_case_comm(ctypes.byref(c), np_xi, np_eta, comm, device, ctypes.byref(m.t)),
                    "roms_gpu_init_case_comm")
         m.LLm, m.MMm, m.N, m.NT = LLm, MMm, N, NT
+        m.salinity = bool(salinity)
         m.jnode, m.inode = divmod(rank, np_xi)
         m.Lm, m.iSW = rank_extent(LLm, np_xi, m.inode)
         m.Mm, m.jSW = rank_extent(MMm, np_eta, m.jnode)
@@ -349,6 +361,7 @@ class Model:
         m = cls()
         m._chk(m.L.roms_gpu_init(ctypes.byref(dims), ctypes.byref(cfg), device, None), "roms_gpu_init")
         m.LLm, m.MMm, m.N, m.NT = dims.Lm, dims.Mm, dims.N, dims.NT
+        m.salinity = bool(cfg.salinity)
         m.shape2 = (dims.Mm + 4, dims.Lm + 4)
         return m
 
@@ -661,6 +674,47 @@ class Model:
 
     def io_wait(self):
         self._chk(self.L.roms_gpu_io_wait(), "io_wait")
+
+    # ---- time-averaged output (calc_avg_ocean_vars / wrt_avg_ocean_vars, basic_output.F) ----
+    def avg_begin(self, mask=WRT_DEFAULT):
+        """Arm averaging of the WRT bits in `mask` (0: disarm and free)."""
+        self._chk(self.L.roms_gpu_avg_begin(mask), "avg_begin")
+
+    def calc_avg(self, time):
+        """One sample after a step (main.F:486): zeta/ubar/vbar(knew), u/v/t(nstp), `time` at n+1."""
+        self._chk(self.L.roms_gpu_calc_avg(ctypes.byref(self.t), time), "calc_avg")
+
+    def wrt_avg(self, path, rec, total_rec, period):
+        """wrt_avg_ocean_vars: record rec of this rank's averages file; starts a fresh window."""
+        self._chk(self.L.roms_gpu_wrt_avg(path.encode(), rec, total_rec, period, ctypes.byref(self.t)), "wrt_avg")
+
+    def avg_state(self):
+        """(navg, t_avg, mask) of the open window."""
+        n, m, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        self._chk(self.L.roms_gpu_avg_state(ctypes.byref(n), ctypes.byref(t), ctypes.byref(m)), "avg_state")
+        return n.value, t.value, m.value
+
+    def avg(self, name, itrc=0):
+        """The running mean of `name` (AVG_FIELDS; "t" with itrc 0.., or "temp" /
+        "salt") as a (levels, j, i) array like get(); only the reference's
+        write ranges (dimensions.F:40-45) are specified."""
+        if name not in AVG_FIELDS:
+            raise ValueError("avg: unknown field %s" % name)
+        bit, lev = AVG_FIELDS[name]
+        if name == "salt":
+            itrc = 1
+            if self.NT < 2 or not self.salinity:
+                raise RomsGpuError("avg: this run has no salinity")
+        levels = (1, self.N, self.N + 1)[lev]
+        a = np.empty(levels * self.shape2[0] * self.shape2[1], dtype=np.float64)
+        self._chk(self.L.roms_gpu_avg_copy_out(bit, itrc + 1, a.ctypes.data, a.size), "avg_copy_out " + name)
+        return a.reshape((levels,) + self.shape2)
+
+    def step_avg(self, n, dt):
+        """n times: one step, then one sample at self.time(dt)."""
+        for _ in range(n):
+            self._r("step")
+            self.calc_avg(self.time(dt))
 
     def get_init(self, path, req_rec, tindx):
         """get_init(req_rec, tindx); returns 0 (read) or 1 (exact restart not possible)."""
