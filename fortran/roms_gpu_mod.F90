@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 25 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 26 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -295,6 +295,40 @@ module roms_gpu_mod
       integer(c_long), value :: count
     end function
     integer(c_int) function roms_gpu_time_calc_avg(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(in) :: t
+      real(c_double), intent(out) :: ms
+    end function
+    ! z-level slices (k_zslice.hip): calc_zslice / wrt_zslice of zslice_output.F
+    integer(c_int) function roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg) bind(c)
+      import :: c_int, c_double
+      integer(c_int), value :: what, ndep, nt_z, do_avg
+      real(c_double), intent(in) :: vecdep(*)
+      integer(c_int), intent(in) :: trc2zsc(*)
+    end function
+    integer(c_int) function roms_gpu_calc_zslice(t) bind(c)
+      import :: c_int, roms_tlev
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_wrt_zslice(path, rec, total_rec, time, t) bind(c)
+      import :: c_int, c_double, c_char, roms_tlev
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: time
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_zslice_state(navg, what, ndep, do_avg) bind(c)
+      import :: c_int
+      integer(c_int), intent(out) :: navg, what, ndep, do_avg
+    end function
+    integer(c_int) function roms_gpu_zslice_copy_out(what_bit, q, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: what_bit, q
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_time_calc_zslice(n, t, ms) bind(c)
       import :: c_int, c_double, roms_tlev
       integer(c_int), value :: n
       type(roms_tlev), intent(in) :: t

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 25
+#define ROMS_GPU_ABI_VERSION 26
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -569,6 +569,61 @@ int roms_gpu_wrt_avg(const char *path, int rec, int total_rec, double period, co
 int roms_gpu_avg_state(int *navg, double *t_avg, int *mask);
 int roms_gpu_avg_copy_out(int wrt_bit, int itrc, double *dst, long count);
 int roms_gpu_time_calc_avg(int n, const roms_tlev *t, double *ms);
+/* ---- z-level slices on the device (ABI 26): calc_zslice / sigma_to_z /
+ * calc_average / wrt_zslice of zslice_output.F.  u, v and chosen tracers, slot
+ * t->nnew (the slot roms_gpu_wrt_his samples), interpolated from the model
+ * levels to fixed depths relative to the free surface (negative: below it),
+ * as a snapshot or as a running mean (do_avg).  Slicing is off until
+ * roms_gpu_zslice_begin arms it and roms_gpu_step never samples by itself.
+ * roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg): what is a
+ * sum of ROMS_ZSL_* bits; it allocates ndep planes per selected field (one per
+ * tracer of trc2zsc, 1-based indices, nt_z of them; both ignored without
+ * ROMS_ZSL_T) in the 2-D device layout, and as many again for the means when
+ * do_avg, all zero, and sets navg = 0.  what == 0 disarms and frees; calling
+ * it again re-arms from scratch; roms_gpu_finalize frees.  It refuses (-1)
+ * ndep outside 1..ROMS_ZSL_MAXDEP, a tracer index outside 1..NT, ROMS_ZSL_T
+ * with nt_z < 1, and N < 2.  Depths may be unsorted and may repeat.
+ * For each cell i = 1..Lm, j = 1..Mm and depth zlev, with zz(k) = z_r(k) -
+ * z_w(N) (k = 1..N), zz(0) = z_w(0) - z_w(N), zz(N+1) = 0 (u, v points: the
+ * mean of the two rho columns in every term) and dpth = zz(N+1) - zz(0), the
+ * first test that holds decides: rmask(i,j) < 0.5 (at u, v points too) -> 0;
+ * dpth*(zlev-zz(N+1)) > 0 -> 0; dpth*(zlev-zz(N)) > 0 -> var(N) +
+ * (zlev-zz(N))*(var(N)-var(N-1))/(zz(N)-zz(N-1)); dpth*(zz(0)-zlev) > 0 -> 0;
+ * dpth*(zz(1)-zlev) > 0 -> var(1) - (zz(1)-zlev)*(var(2)-var(1))/(zz(2)-zz(1));
+ * else the first k = N-1..1 with (zz(k+1)-zlev)*(zlev-zz(k)) >= 0 ->
+ * (var(k)*(zz(k+1)-zlev) + var(k+1)*(zlev-zz(k)))/(zz(k+1)-zz(k)).
+ * roms_gpu_calc_zslice: one sample on the library stream, one kernel launch
+ * whatever the fields and depths.  With do_avg the same launch advances the
+ * means: navg += 1, coef = 1/navg, X_avg = X_avg*(1-coef) + X*coef; at
+ * coef == 1 the old mean is not read.  Returns -4 when not armed.
+ * roms_gpu_wrt_zslice writes record rec (rec 1 creates the file) through the
+ * writer of roms_gpu_wrt_his (roms_gpu_io_wait joins it): without do_avg it
+ * samples first; with do_avg it needs navg > 0 (else -4, nothing written).
+ * The file holds the dimension depth, depth(depth) = vecdep, ocean_time =
+ * time, time_step as the other files of this writer, every sliced tracer
+ * under its roms_gpu_io_tracer_name name on (time, depth, eta_rho, xi_rho), u
+ * on (.., eta_rho, xi_u), v on (.., eta_v, xi_rho), the history file's long
+ * names and units -- with do_avg 'averaged' straight ahead of a tracer's long
+ * name and 'averaged ' ahead of u's and v's, as the reference has them -- and
+ * the partition attribute when decomposed.  Points of the partition's write
+ * range outside 1..Lm x 1..Mm hold 0.  Afterwards navg = 0.
+ * roms_gpu_zslice_state: a query (any pointer may be NULL).
+ * roms_gpu_zslice_copy_out: the current slices, or with do_avg the means, of
+ * ONE ROMS_ZSL_* bit (q = 1..nt_z picks the tracer for ROMS_ZSL_T, ignored
+ * otherwise) as (ndep, Mm+4, Lm+4) in the host layout; count must be that
+ * size.
+ * roms_gpu_time_calc_zslice: n samples between two events on the library
+ * stream, total milliseconds (with do_avg they go on from the open window). */
+#define ROMS_ZSL_T 1
+#define ROMS_ZSL_U 2
+#define ROMS_ZSL_V 4
+#define ROMS_ZSL_MAXDEP 32
+int roms_gpu_zslice_begin(int what, int ndep, const double *vecdep, int nt_z, const int *trc2zsc, int do_avg);
+int roms_gpu_calc_zslice(const roms_tlev *t);
+int roms_gpu_wrt_zslice(const char *path, int rec, int total_rec, double time, const roms_tlev *t);
+int roms_gpu_zslice_state(int *navg, int *what, int *ndep, int *do_avg);
+int roms_gpu_zslice_copy_out(int what_bit, int q, double *dst, long count);
+int roms_gpu_time_calc_zslice(int n, const roms_tlev *t, double *ms);
 /* t_vname/t_units/t_lname of tracer itrc (tracers.opt); default temp, salt, trcNN */
 int roms_gpu_io_tracer_name(int itrc, const char *name, const char *units, const char *long_name);
 /* Returns 0 (read), 1 (tindx 2: records not consecutive steps, nothing read),

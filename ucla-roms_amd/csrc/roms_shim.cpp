@@ -398,6 +398,7 @@ hipError_t dev_alloc(double*& p, long n) {
 void free_all() {
   io_free();
   avg_free();
+  zslice_free();
   frc_free();
   if (g.small) { (void)hipFree(g.small); g.small = nullptr; g.small_n = 0; }
   if (g.stage) { (void)hipFree(g.stage); g.stage = nullptr; g.stage_n = 0; }
@@ -462,6 +463,7 @@ long roms::shim_field_dev_count(int id) { return (id >= 0 && id < ROMS_NFIELDS) 
 hipError_t roms::shim_field_h2d(int id, double* dev, const double* host) { return field_h2d(id, dev, host); }
 hipError_t roms::shim_rows_h2d(double* dev, const double* host, long rows) { return rows_h2d(dev, host, rows); }
 hipError_t roms::shim_rows_d2h(double* host, const double* dev, long rows) { return rows_d2h(host, dev, rows); }
+bool roms::shim_vgrid_valid() { return g.vgrid_valid; }
 double* roms::shim_scratch_small(long n) {
   if (g.small_n < n) {
     if (g.small) { (void)hipStreamSynchronize(g.s); (void)hipFree(g.small); g.small = nullptr; }

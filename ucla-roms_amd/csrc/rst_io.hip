@@ -16,7 +16,9 @@
 // reference does it, upload of packed slabs, one scatter kernel per variable,
 // and the reference's exchange_xxx after every field.  Averages records
 // (wrt_avg_ocean_vars, basic_output.F:421-515) take the same write path with
-// the running means of k_avg.hip in place of the fields.
+// the running means of k_avg.hip in place of the fields, and slices records
+// (zslice_output.F:284-410) with the planes of k_zslice.hip on a depth
+// dimension in place of s_rho.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -108,6 +110,7 @@ struct OutVar {
   std::string name, lname, units;
   char grid;      // 'r', 'u', 'v'
   int levels;     // 0: 2-D; N or N+1
+  int depth = 0;  // slices: planes on the depth dimension (levels 0)
   Slab slab;
   long off = 0;   // offset in the staging buffer (elements)
 };
@@ -267,15 +270,42 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   return v;
 }
 
+// the variable list of a slices record (def_vars_zslice): each sliced tracer
+// under its name, u, v, ndep planes each.  The reference writes 'averaged'
+// straight ahead of a tracer's long name and 'averaged ' ahead of u's and v's
+std::vector<OutVar> zslice_vars(const ShimState& S, const ZslView& zv) {
+  const Bounds& b = S.d->b;
+  const Part p = part_of(*S.dims);
+  std::vector<OutVar> v;
+  auto add = [&](const std::string& name, const std::string& ln, const std::string& un, char g, const double* base) {
+    OutVar o;
+    o.name = name; o.lname = ln; o.units = un; o.grid = g; o.levels = 0; o.depth = zv.ndep;
+    o.slab = slab_of(b, p, base, g, zv.ndep, b.n2);
+    v.push_back(o);
+  };
+  if (zv.what & ROMS_ZSL_T) {
+    std::vector<std::string> nm, un, ln;
+    tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
+    for (size_t q = 0; q < zv.trc.size(); q++) {
+      const int it = zv.trc[q] - 1;
+      add(nm[it], zv.do_avg ? "averaged" + ln[it] : ln[it], un[it], 'r', zv.do_avg ? zv.t_avg[q] : zv.t[q]);
+    }
+  }
+  const std::string av = zv.do_avg ? "averaged " : "";
+  if (zv.what & ROMS_ZSL_U) add("u", av + "u-momentum component", "meter second-1", 'u', zv.do_avg ? zv.u_avg : zv.u);
+  if (zv.what & ROMS_ZSL_V) add("v", av + "v-momentum component", "meter second-1", 'v', zv.do_avg ? zv.v_avg : zv.v);
+  return v;
+}
+
 void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst, bool avg = false,
-                 double period = 0.0) {
+                 double period = 0.0, const ZslView* zv = nullptr) {
   const Part p = part_of(*S.dims);
   const int N = S.d->b.N;
   // create_file (roms_read_write.F:1161-1208): ocean_time first, then the global attributes
   const int dtm = f.add_dim("time", 0);
   f.add_var("ocean_time", nc::NC_DOUBLE, {dtm},
             {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
-  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : "ROMS history file");
+  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : "ROMS history file");
   if (avg) {   // the window length as F12.1, left-adjusted (basic_output.F:451-455, 705)
     char tb[64];
     snprintf(tb, sizeof tb, "%.1f seconds", period);
@@ -286,12 +316,17 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
             {nc::Att::str("long_name", "time step and record numbers from initialization")});
   const int dxr = f.add_dim("xi_rho", p.xi_rho), dxu = f.add_dim("xi_u", p.xi_u);
   const int dyr = f.add_dim("eta_rho", p.eta_rho), dyv = f.add_dim("eta_v", p.eta_v);
-  int dzr = -1, dzw = -1;
+  int dzr = -1, dzw = -1, ddp = -1;
+  if (zv) {   // def_vars_zslice: depth(depth) = vecdep
+    ddp = f.add_dim("depth", zv->ndep);
+    f.add_var("depth", nc::NC_DOUBLE, {ddp});
+  }
   for (const OutVar& o : vars) {
     const int dx = o.grid == 'u' ? dxu : dxr, dy = o.grid == 'v' ? dyv : dyr;
     std::vector<int> dims{dtm};
     if (o.levels == N) { if (dzr < 0) dzr = f.add_dim("s_rho", N); dims.push_back(dzr); }
     if (o.levels == N + 1) { if (dzw < 0) dzw = f.add_dim("s_w", N + 1); dims.push_back(dzw); }
+    if (o.depth) dims.push_back(ddp);
     dims.push_back(dy);
     dims.push_back(dx);
     std::vector<nc::Att> at{nc::Att::str("long_name", o.lname)};
@@ -301,7 +336,7 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
 }
 
 int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask,
-                 bool avg = false, double period = 0.0) {
+                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
@@ -315,7 +350,7 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
     time = av->t_avg;
   }
   if ((r = io_join(*S.err))) return r;
-  std::vector<OutVar> vars = record_vars(S, *t, rst, mask, av);
+  std::vector<OutVar> vars = zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av);
   size_t n = 0;
   for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
   if (!io.drain) {
@@ -358,7 +393,8 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   const roms_tlev tl = *t;
   const bool create = rec == 1;
   nc::File* proto = new nc::File();
-  if (create) define_file(*proto, S, vars, rst, avg, period);
+  if (create) define_file(*proto, S, vars, rst, avg, period, zv);
+  const std::vector<double> depths = zv && create ? zv->vecdep : std::vector<double>();
   if (avg) avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
   io.job.status = 0;
   io.job.err.clear();
@@ -378,6 +414,7 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
       f->put_double(vt, r0, &time);
       const int ts[6] = {tl.iic, rec, total_rec, 0, 0, 0};   // write_time_step (basic_output.F:1120-1150)
       f->put_int(vs, r0, ts);
+      if (!depths.empty()) f->put_double(f->find_var("depth"), 0, depths.data());
       for (const OutVar& o : vars) {
         const int id = f->find_var(o.name);
         if (id < 0) throw std::runtime_error(fpath + ": variable " + o.name + " not defined");
@@ -395,6 +432,10 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
 }
 
 }  // namespace
+
+int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv) {
+  return write_record(path, rec, total_rec, time, t, false, 0, false, 0.0, &zv);
+}
 }  // namespace roms
 
 using namespace roms;

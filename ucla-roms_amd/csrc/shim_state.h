@@ -69,6 +69,23 @@ struct AvgView {
 const AvgView& avg_view();
 void avg_window_written();   // wrt_avg: navg = 0, the next sample starts a fresh window
 void avg_free();             // roms_gpu_finalize
+// Z-level slices (k_zslice.hip): ndep planes per sliced field in the 2-D
+// device layout, zero outside cells 1..Lm x 1..Mm, for rst_io.hip's writer.
+struct ZslView {
+  int what = 0;        // ROMS_ZSL_* bits armed (0: slicing off)
+  int ndep = 0;
+  bool do_avg = false;
+  int navg = 0;        // samples in the open window (do_avg)
+  std::vector<double> vecdep;
+  std::vector<int> trc;                // tracer index (1..NT) of each sliced tracer
+  std::vector<double*> t, t_avg;       // one per sliced tracer
+  double *u = nullptr, *v = nullptr, *u_avg = nullptr, *v_avg = nullptr;
+};
+// rst_io.hip: record rec of a slices file from the view's planes (the means
+// when do_avg), through the snapshot and writer thread of the other records
+int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv);
+void zslice_free();            // roms_gpu_finalize
+bool shim_vgrid_valid();       // the stored Hz, z_r, z_w are set_depth's own (VGrid may stand in for them)
 double* shim_scratch_small(long n);      // small device scratch owned by the context (>= n doubles)
 // step3d_uv2's closed-edge column lists (k_step3d_uv.hip): (dir, i, j) triples
 void uv2_edge_lists(const Bounds& b, std::vector<int>& couple, std::vector<int>& flux);

@@ -147,6 +147,13 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_avg_state.argtypes = [P(ctypes.c_int), P(ctypes.c_double), P(ctypes.c_int)]
     L.roms_gpu_avg_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
     L.roms_gpu_time_calc_avg.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_zslice_begin.argtypes = [ctypes.c_int, ctypes.c_int, P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int),
+                                        ctypes.c_int]
+    L.roms_gpu_calc_zslice.argtypes = [P(Tlev)]
+    L.roms_gpu_wrt_zslice.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, P(Tlev)]
+    L.roms_gpu_zslice_state.argtypes = [P(ctypes.c_int)] * 4
+    L.roms_gpu_zslice_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_time_calc_zslice.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     _lib = L
     return L
 
@@ -214,6 +221,9 @@ WRT_ALL = 8191
 AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=(32, 1), temp=(32, 1), salt=(32, 1),
                   rho=(64, 1), omega=(128, 2), Akv=(256, 2), Akt=(512, 2), Aks=(1024, 2), hbls=(2048, 0),
                   hbbl=(4096, 0))
+# ROMS_ZSL_* of include/roms_gpu.h (zslice_output.opt wrt_*_zsl switches)
+ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
+ZSL_MAXDEP = 32
 # enum roms_routine of include/roms_gpu.h
 ROUTINES = ("rho_eos", "set_HUV", "omega", "prsgrd", "pre_step3d", "set_HUV1", "step3d_uv1", "visc3d", "step2d",
             "step3d_uv2", "step3d_t", "t3dmix", "lmd_vmix",
@@ -715,6 +725,49 @@ class Model:
         for _ in range(n):
             self._r("step")
             self.calc_avg(self.time(dt))
+
+    # ---- z-level slices (calc_zslice / wrt_zslice, zslice_output.F) ----
+    def zslice_begin(self, depths, what=ZSL_U | ZSL_V, tracers=(1, 2), avg=False):
+        """Arm slicing of the ZSL bits in `what` at `depths` (relative to the free surface, negative below it);
+        `tracers`: 1-based indices sliced with ZSL_T; avg: running means sampled by every calc_zslice.
+        what=0 disarms and frees."""
+        d = np.ascontiguousarray(depths, dtype=np.float64).ravel()
+        tr = np.ascontiguousarray(tracers if what & ZSL_T else (), dtype=np.int32).ravel()
+        self._chk(self.L.roms_gpu_zslice_begin(what, d.size, d.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), tr.size,
+                                               tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(avg)), "zslice_begin")
+        self._zsl_tracers = [int(x) for x in tr] if what else []
+
+    def calc_zslice(self):
+        """One sample of u, v, t(nnew) after a step; with avg it also advances the means."""
+        self._chk(self.L.roms_gpu_calc_zslice(ctypes.byref(self.t)), "calc_zslice")
+
+    def wrt_zslice(self, path, rec, total_rec, time):
+        """wrt_zslice: record rec of this rank's slices file (samples first without avg); starts a fresh window."""
+        self._chk(self.L.roms_gpu_wrt_zslice(path.encode(), rec, total_rec, time, ctypes.byref(self.t)), "wrt_zslice")
+
+    def zslice_state(self):
+        """(navg, what, ndep, avg) of the armed slicing."""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._chk(self.L.roms_gpu_zslice_state(*[ctypes.byref(x) for x in v]), "zslice_state")
+        return v[0].value, v[1].value, v[2].value, bool(v[3].value)
+
+    def zslice(self, name, q=None):
+        """The current slices (the means with avg) of "u", "v", "t" (q = 1..nt_z in the order of `tracers`) or of
+        "temp" / "salt" when they are among the sliced tracers, as (ndep, j, i) like get(); cells outside
+        1..Lm x 1..Mm hold 0."""
+        if name in ("temp", "salt"):
+            it = 1 if name == "temp" else 2
+            if it not in getattr(self, "_zsl_tracers", []) or (it == 2 and not self.salinity):
+                raise RomsGpuError("zslice: %s is not being sliced" % name)
+            name, q = "t", self._zsl_tracers.index(it) + 1
+        if name not in ("t", "u", "v"):
+            raise ValueError("zslice: unknown field %s" % name)
+        bit = dict(t=ZSL_T, u=ZSL_U, v=ZSL_V)[name]
+        ndep = self.zslice_state()[2]
+        a = np.empty(max(ndep, 1) * self.shape2[0] * self.shape2[1], dtype=np.float64)
+        self._chk(self.L.roms_gpu_zslice_copy_out(bit, 1 if q is None else q, a.ctypes.data, a.size),
+                  "zslice_copy_out " + name)
+        return a.reshape((ndep,) + self.shape2)
 
     def get_init(self, path, req_rec, tindx):
         """get_init(req_rec, tindx); returns 0 (read) or 1 (exact restart not possible)."""
