@@ -58,7 +58,11 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 26 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 27 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  ! extraction variables (ROMS_EXT_*); UP, VP, W, BGC are parsed and reported, not produced
+  integer(c_int), parameter :: ROMS_EXT_ZETA = 1, ROMS_EXT_UBAR = 2, ROMS_EXT_VBAR = 4, ROMS_EXT_U = 8, &
+                               ROMS_EXT_V = 16, ROMS_EXT_TEMP = 32, ROMS_EXT_SALT = 64, ROMS_EXT_UP = 128, &
+                               ROMS_EXT_VP = 256, ROMS_EXT_W = 512, ROMS_EXT_BGC = 1024
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -333,6 +337,78 @@ module roms_gpu_mod
       integer(c_int), value :: n
       type(roms_tlev), intent(in) :: t
       real(c_double), intent(out) :: ms
+    end function
+    ! child-boundary extraction (k_extract.hip): do_extract_data of extract_data.F
+    integer(c_int) function roms_gpu_extract_begin(N_chd, theta_s_chd, theta_b_chd, hc_chd) bind(c)
+      import :: c_int, c_double
+      integer(c_int), value :: N_chd
+      real(c_double), value :: theta_s_chd, theta_b_chd, hc_chd
+    end function
+    integer(c_int) function roms_gpu_extract_angler(angler, count) bind(c)
+      import :: c_int, c_long, c_double
+      real(c_double), intent(in) :: angler(*)
+      integer(c_long), value :: count
+    end function
+    ! ang: c_null_ptr for a scalar object, else c_loc of the angles
+    integer(c_int) function roms_gpu_extract_add_object(name, dname, np_global, ipos, jpos, ang, output_vars) bind(c)
+      import :: c_int, c_long, c_double, c_char, c_ptr
+      character(kind=c_char), intent(in) :: name(*), dname(*), output_vars(*)
+      integer(c_long), value :: np_global
+      real(c_double), intent(in) :: ipos(*), jpos(*)
+      type(c_ptr), value :: ang
+    end function
+    integer(c_int) function roms_gpu_extract_objects_file(path) bind(c)
+      import :: c_int, c_char
+      character(kind=c_char), intent(in) :: path(*)
+    end function
+    integer(c_int) function roms_gpu_calc_extract(t) bind(c)
+      import :: c_int, roms_tlev
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_wrt_extract(path, rec, total_rec, time, t) bind(c)
+      import :: c_int, c_double, c_char, roms_tlev
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: time
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_extract_state(nobj, mismatch, N_chd, np_total, need_huv) bind(c)
+      import :: c_int
+      integer(c_int), intent(out) :: nobj, mismatch, N_chd, np_total, need_huv
+    end function
+    integer(c_int) function roms_gpu_extract_object_info(iobj, np, start_idx, vars, unsupported, scalar) bind(c)
+      import :: c_int
+      integer(c_int), value :: iobj
+      integer(c_int), intent(out) :: np, start_idx, vars, unsupported, scalar
+    end function
+    integer(c_int) function roms_gpu_extract_object_coef(iobj, grid, ip, jp, coef, cosa, sina) bind(c)
+      import :: c_int, c_double
+      integer(c_int), value :: iobj, grid
+      integer(c_int), intent(out) :: ip(*), jp(*)
+      real(c_double), intent(out) :: coef(*), cosa(*), sina(*)
+    end function
+    integer(c_int) function roms_gpu_extract_child_cs(cs_w) bind(c)
+      import :: c_int, c_double
+      real(c_double), intent(out) :: cs_w(*)
+    end function
+    integer(c_int) function roms_gpu_extract_copy_out(iobj, var_bit, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: iobj, var_bit
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_time_calc_extract(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(in) :: t
+      real(c_double), intent(out) :: ms(2)
+    end function
+    integer(c_int) function roms_gpu_extract_locate(nx, ny, iSW_corn, jSW_corn, npg, ipos, jpos, start_idx, np) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: nx, ny, iSW_corn, jSW_corn
+      integer(c_long), value :: npg
+      real(c_double), intent(in) :: ipos(*), jpos(*)
+      integer(c_int), intent(out) :: start_idx, np
     end function
     integer(c_int) function roms_gpu_io_wait() bind(c)
       import :: c_int

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 26
+#define ROMS_GPU_ABI_VERSION 27
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -624,6 +624,88 @@ int roms_gpu_wrt_zslice(const char *path, int rec, int total_rec, double time, c
 int roms_gpu_zslice_state(int *navg, int *what, int *ndep, int *do_avg);
 int roms_gpu_zslice_copy_out(int what_bit, int q, double *dst, long count);
 int roms_gpu_time_calc_zslice(int n, const roms_tlev *t, double *ms);
+/* ---- child-boundary extraction on the device (ABI 27): do_extract_data of
+ * extract_data.F with remap_src_to_grid of vertical_remapping.F.  An object is
+ * a line of np_global fractional positions (ipos, jpos) in absolute index
+ * space ([0,LLm]x[0,MMm], cell centres at half integers), with an angle per
+ * point (a vector object) or without (ang == NULL, a scalar object), and an
+ * output_vars string.  Extraction is off until an object is added and
+ * roms_gpu_step never samples; extract_period, nrpf_extract and otime stay
+ * with the host.
+ * roms_gpu_extract_begin(N_chd, theta_s_chd, theta_b_chd, hc_chd) clears every
+ * object (disarms) and sets the child's vertical grid: the remap is used
+ * unless all four equal the parent's (parent_child_grid_mismatch); Cs_w_chd
+ * follows set_chd_scoord.  roms_gpu_extract_angler sets the grid angle
+ * (host layout, (Mm+4)*(Lm+4), default 0) ahead of the first object.
+ * roms_gpu_extract_add_object: the rank keeps the FIRST contiguous run of
+ * points with 0 <= ipos-iSW_corn < Lm and 0 <= jpos-jSW_corn < Mm
+ * (find_local_points assumes contiguity: a line that re-enters the subdomain
+ * loses its second run) as start_idx (1-based) and np.  set is the name up to
+ * its first '_', bnd runs from that '_' up to the next one ('grid1_west_r':
+ * 'grid1', '_west'); a variable is called set_var+bnd.  output_vars is
+ * searched for substrings as findstr does: 'zeta', 'temp', 'salt', 'ubar',
+ * 'vbar', 'u' (also found in 'ubar' and 'up'), 'v', 'w', 'up', 'vp', 'bgc'.
+ * ROMS_EXT_UP/VP/W/BGC are not produced (no calc_pflx, wvlcty, BGC here):
+ * they are reported in the object's `unsupported` mask and named in
+ * roms_gpu_last_error while the call returns 0.  'salt' is ignored without
+ * SALINITY.  Refused (-1, nothing armed): a vector variable on a scalar
+ * object; a 3-D variable with the remap when N < 5.  Coefficients follow
+ * compute_coef at rho (+0.5,+0.5), u (+0.5 in i) and v (-0.5 in i, +0.5 in j)
+ * positions with rmask/umask/vmask and coef/sum(coef): a point whose four
+ * corners are masked has NaN coefficients and NaN results, as the reference.
+ * cosa, sina = cos, sin(angler interpolated with the rho coefficients - ang).
+ * roms_gpu_extract_objects_file reads the reference's objects file (netCDF
+ * classic CDF-1/2; each variable one object, (2|3, np) doubles, the point
+ * dimension fastest, attribute output_vars); all objects are added or none.
+ * roms_gpu_calc_extract: one sample, two launches (interpolation of every
+ * object and variable; the remap).  zeta, ubar, vbar from slot t->knew
+ * (ubar: cosa*ui - sina*vi, vbar: sina*ui + cosa*vi); u, v, temp, salt from
+ * slot t->nstp, u and v rotated level by level.  With the remap the parent's
+ * thicknesses are Hz, Hz_u, Hz_v interpolated (Hz_u, Hz_v: set_HUV's of the
+ * step just taken, kept by whole steps while an object needs them), the
+ * child's come from get_child_thickness of their sums, and every profile goes
+ * through remap_src_to_grid onto N_chd layers; otherwise the (N, np) profile
+ * is the result.  On a decomposed run every rank calls it (halo of Hz_u, Hz_v).
+ * roms_gpu_wrt_extract samples, then writes record rec (rec 1 creates the
+ * file; total_rec is unused) through the writer of roms_gpu_wrt_his: one file
+ * per rank; per object with np > 0 the dimension np%03d (its 1-based index),
+ * <set>_time ('Time since 2000', 'second'), 2-D variables on (time, np), 3-D
+ * ones on (time, s_rho = N_chd, np), attributes start, count, dname, dsize,
+ * long_name, units, type double.  The one record dimension is
+ * time_<set of the first object> for every set.
+ * roms_gpu_extract_object_coef: grid 0 rho, 1 u, 2 v; coef is (4, np).
+ * roms_gpu_extract_copy_out: one ROMS_EXT_* bit of object iobj (1-based) from
+ * the last sample as (levels, np), levels = N_chd with the remap else N, or
+ * (np); count must be that size.
+ * roms_gpu_time_calc_extract: n interpolation launches, then n remap launches,
+ * each between two events: ms[0], ms[1] their total milliseconds.
+ * roms_gpu_extract_locate is find_local_points alone, without a device. */
+#define ROMS_EXT_ZETA 1
+#define ROMS_EXT_UBAR 2
+#define ROMS_EXT_VBAR 4
+#define ROMS_EXT_U 8
+#define ROMS_EXT_V 16
+#define ROMS_EXT_TEMP 32
+#define ROMS_EXT_SALT 64
+#define ROMS_EXT_UP 128
+#define ROMS_EXT_VP 256
+#define ROMS_EXT_W 512
+#define ROMS_EXT_BGC 1024
+int roms_gpu_extract_begin(int N_chd, double theta_s_chd, double theta_b_chd, double hc_chd);
+int roms_gpu_extract_angler(const double *angler, long count);
+int roms_gpu_extract_add_object(const char *name, const char *dname, long np_global, const double *ipos,
+                                const double *jpos, const double *ang, const char *output_vars);
+int roms_gpu_extract_objects_file(const char *path);
+int roms_gpu_calc_extract(const roms_tlev *t);
+int roms_gpu_wrt_extract(const char *path, int rec, int total_rec, double time, const roms_tlev *t);
+int roms_gpu_extract_state(int *nobj, int *mismatch, int *N_chd, int *np_total, int *need_huv);
+int roms_gpu_extract_object_info(int iobj, int *np, int *start_idx, int *vars, int *unsupported, int *scalar);
+int roms_gpu_extract_object_coef(int iobj, int grid, int *ip, int *jp, double *coef, double *cosa, double *sina);
+int roms_gpu_extract_child_cs(double *cs_w);
+int roms_gpu_extract_copy_out(int iobj, int var_bit, double *dst, long count);
+int roms_gpu_time_calc_extract(int n, const roms_tlev *t, double *ms);
+int roms_gpu_extract_locate(int nx, int ny, int iSW_corn, int jSW_corn, long npg, const double *ipos,
+                            const double *jpos, int *start_idx, int *np);
 /* t_vname/t_units/t_lname of tracer itrc (tracers.opt); default temp, salt, trcNN */
 int roms_gpu_io_tracer_name(int itrc, const char *name, const char *units, const char *long_name);
 /* Returns 0 (read), 1 (tindx 2: records not consecutive steps, nothing read),

@@ -56,9 +56,11 @@ struct Ctx {
   int rho_slot = 0;
   // Hz_u/Hz_v (set_HUV's cell heights at u/v points) are read by no kernel of
   // the step, only by the reference's extract_data.F:726: whole steps store
-  // them when the host registered either for transfer or set
-  // ROMS_GPU_HZ_UV=1; otherwise they go stale and reading them fails
+  // them when the host registered either for transfer, set
+  // ROMS_GPU_HZ_UV=1 or armed an extraction object that remaps u or v
+  // (k_extract.hip); otherwise they go stale and reading them fails
   bool hzuv_env = false;
+  bool hzuv_ext = false;      // an armed extraction object reads them (k_extract.hip)
   bool hzuv_valid = true;
   bool rho_reuse = true;      // ROMS_GPU_RHO_REUSE=0 turns the skip off
   // The stored Hz, z_r, z_w are what set_depth formed from z_sd, h, hinv and
@@ -399,6 +401,7 @@ void free_all() {
   io_free();
   avg_free();
   zslice_free();
+  extract_free();
   frc_free();
   if (g.small) { (void)hipFree(g.small); g.small = nullptr; g.small_n = 0; }
   if (g.stage) { (void)hipFree(g.stage); g.stage = nullptr; g.stage_n = 0; }
@@ -464,6 +467,8 @@ hipError_t roms::shim_field_h2d(int id, double* dev, const double* host) { retur
 hipError_t roms::shim_rows_h2d(double* dev, const double* host, long rows) { return rows_h2d(dev, host, rows); }
 hipError_t roms::shim_rows_d2h(double* host, const double* dev, long rows) { return rows_d2h(host, dev, rows); }
 bool roms::shim_vgrid_valid() { return g.vgrid_valid; }
+void roms::shim_extract_huv(bool on) { g.hzuv_ext = on; }
+bool roms::shim_hzuv_valid() { return g.hzuv_valid; }
 double* roms::shim_scratch_small(long n) {
   if (g.small_n < n) {
     if (g.small) { (void)hipStreamSynchronize(g.s); (void)hipFree(g.small); g.small = nullptr; }
@@ -1091,6 +1096,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     g.d.halo = &g.halo;
   }
   g.hzuv_env = env_on("ROMS_GPU_HZ_UV");
+  g.hzuv_ext = false;
   g.hzuv_valid = true;
   g.use_graphs = !env_on("ROMS_GPU_NO_GRAPH") && halo_graph_safe(g.d.halo);
   g.rho_reuse = !env_off("ROMS_GPU_RHO_REUSE");
@@ -1489,7 +1495,7 @@ int roms_gpu_step(roms_tlev* t) {
     }
   }
   const bool first = (t->iic == t->forw_start);
-  const bool store_huv = g.hzuv_env || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
+  const bool store_huv = g.hzuv_env || g.hzuv_ext || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
   g.hzuv_valid = store_huv;
   if (!g.use_graphs || first) {
     enqueue_step(t, rho_current, store_huv);
@@ -1742,7 +1748,7 @@ int roms_gpu_time_routine(int routine, int nsteps, roms_tlev* t, double* avg_ms,
     t->nfast = g.cfg.nfast;
     const int r = frc_step_prepare(g.s, g.d, g.cfg.dt, *t, g.err);   // in-step forcing, as roms_gpu_step
     if (r) { g.timed = -1; return r; }
-    const bool store_huv = g.hzuv_env || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
+    const bool store_huv = g.hzuv_env || g.hzuv_ext || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
     g.hzuv_valid = store_huv;
     enqueue_step(t, g.rho_reuse && g.rho_slot == t->nrhs, store_huv);
   }

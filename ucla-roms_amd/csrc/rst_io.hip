@@ -436,6 +436,98 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
 int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv) {
   return write_record(path, rec, total_rec, time, t, false, 0, false, 0.0, &zv);
 }
+
+int io_writer_join(std::string& err) { return io_join(err); }
+
+// One record of an extraction file (create_edata_vars / create_var / the
+// ncwrite calls of do_extract_data, extract_data.F:563-959): R.dev holds the
+// record packed on the library stream; the copy to the host runs on the drain
+// stream and the writer thread defines (rec 1) and writes the file.  The
+// classic format has one record dimension, so every set's variables share
+// R.time_dim; each set still has its own <set>_time variable.
+int extract_write(const char* path, int rec, double time, const ExtRecord& R) {
+  ShimState S;
+  int r = shim_enter(S, true);
+  if (r) return r;
+  if ((r = io_join(*S.err))) return r;
+  const size_t n = R.n < 1 ? 1 : R.n;
+  if (!io.drain) {
+    if (hipStreamCreateWithFlags(&io.drain, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&io.packed, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&io.landed, hipEventDisableTiming) != hipSuccess) {
+      *S.err = "roms_gpu_wrt_extract: stream/event creation failed";
+      return -2;
+    }
+  }
+  if (io.pinned_n < n) {
+    if (io.pinned) (void)hipHostFree(io.pinned);
+    io.pinned = nullptr;
+    io.pinned_n = 0;
+    if (hipHostMalloc(&io.pinned, n * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      *S.err = "roms_gpu_wrt_extract: pinned staging allocation failed";
+      return -2;
+    }
+    io.pinned_n = n;
+  }
+  if (hipEventRecord(io.packed, S.s) != hipSuccess || hipStreamWaitEvent(io.drain, io.packed, 0) != hipSuccess ||
+      (R.n && hipMemcpyAsync(io.pinned, R.dev, R.n * sizeof(double), hipMemcpyDeviceToHost, io.drain) != hipSuccess) ||
+      hipEventRecord(io.landed, io.drain) != hipSuccess) {
+    *S.err = "roms_gpu_wrt_extract: snapshot enqueue failed";
+    return -2;
+  }
+  const std::string fpath(path);
+  const bool create = rec == 1;
+  nc::File* proto = new nc::File();
+  if (create) {
+    const int dtm = proto->add_dim(R.time_dim, 0);
+    global_atts(*proto, S, "ROMS extraction file");
+    for (const std::string& tv : R.time_vars)
+      proto->add_var(tv, nc::NC_DOUBLE, {dtm}, {nc::Att::str("long_name", "Time since 2000"), nc::Att::str("units", "second")});
+    std::vector<int> dnp;
+    for (const auto& d : R.dims) dnp.push_back(proto->add_dim(d.first, d.second));
+    const int dz = R.s_rho > 0 ? proto->add_dim("s_rho", R.s_rho) : -1;
+    for (const ExtFileVar& v : R.vars) {
+      std::vector<int> dims{dtm};
+      if (v.levels) dims.push_back(dz);
+      dims.push_back(dnp[v.dim_np]);
+      proto->add_var(v.name, nc::NC_DOUBLE, dims,
+                     {nc::Att::i("start", {v.start}), nc::Att::i("count", {v.count}), nc::Att::str("dname", v.dname),
+                      nc::Att::i("dsize", {v.dsize}), nc::Att::str("long_name", v.lname), nc::Att::str("units", v.units)});
+    }
+  }
+  const ExtRecord rc = R;
+  io.job.status = 0;
+  io.job.err.clear();
+  io.job.running = true;
+  hipEvent_t landed = io.landed;
+  const double* host = io.pinned;
+  IoJob* job = &io.job;
+  io.job.th = std::thread([=]() {
+    std::unique_ptr<nc::File> f(proto);
+    try {
+      if (hipEventSynchronize(landed) != hipSuccess) throw std::runtime_error("snapshot copy failed");
+      if (create) f->create(fpath);
+      else f->open(fpath, true);
+      const int64_t r0 = rec - 1;
+      for (const std::string& tv : rc.time_vars) {
+        const int id = f->find_var(tv);
+        if (id < 0) throw std::runtime_error(fpath + ": not an extraction file of these objects (no " + tv + ")");
+        f->put_double(id, r0, &time);
+      }
+      for (const ExtFileVar& v : rc.vars) {
+        const int id = f->find_var(v.name);
+        if (id < 0) throw std::runtime_error(fpath + ": variable " + v.name + " not defined");
+        if (f->vars[id].count() != (int64_t)v.n) throw std::runtime_error(fpath + ": variable " + v.name + " has another shape");
+        f->put_double(id, r0, host + v.off);
+      }
+      f->close();
+    } catch (const std::exception& e) {
+      job->status = -7;
+      job->err = std::string("roms_gpu_wrt_extract: ") + e.what();
+    }
+  });
+  return 0;
+}
 }  // namespace roms
 
 using namespace roms;

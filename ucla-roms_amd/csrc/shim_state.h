@@ -86,6 +86,31 @@ struct ZslView {
 int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv);
 void zslice_free();            // roms_gpu_finalize
 bool shim_vgrid_valid();       // the stored Hz, z_r, z_w are set_depth's own (VGrid may stand in for them)
+// Child-boundary extraction (k_extract.hip): one record of an extraction file
+// for rst_io.hip's writer thread.  Every variable lies packed, (levels, np)
+// point-fastest, in one device buffer that the library stream has filled.
+struct ExtFileVar {
+  std::string name;
+  int dim_np = -1;       // index into ExtRecord::dims of its point dimension
+  bool levels = false;   // on (time, s_rho, np) instead of (time, np)
+  int start = 0, count = 0, dsize = 0;   // the object's start_idx, np and global length
+  std::string dname, lname, units;
+  long off = 0, n = 0;   // its elements in the packed buffer
+};
+struct ExtRecord {
+  std::string time_dim;                             // the record dimension
+  std::vector<std::string> time_vars;               // <set>_time of every set, in first-appearance order
+  std::vector<std::pair<std::string, int>> dims;    // np%03d of every object present
+  int s_rho = 0;                                    // N_chd (0: no 3-D variable)
+  std::vector<ExtFileVar> vars;
+  const double* dev = nullptr;
+  size_t n = 0;
+};
+int extract_write(const char* path, int rec, double time, const ExtRecord& R);
+int io_writer_join(std::string& err);   // joins the writer thread (0 or its error)
+void extract_free();                    // roms_gpu_finalize
+void shim_extract_huv(bool on);         // whole steps store Hz_u/Hz_v while an armed object reads them
+bool shim_hzuv_valid();                 // the stored Hz_u/Hz_v are set_HUV's of the last step
 double* shim_scratch_small(long n);      // small device scratch owned by the context (>= n doubles)
 // step3d_uv2's closed-edge column lists (k_step3d_uv.hip): (dir, i, j) triples
 void uv2_edge_lists(const Bounds& b, std::vector<int>& couple, std::vector<int>& flux);

@@ -154,6 +154,21 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_zslice_state.argtypes = [P(ctypes.c_int)] * 4
     L.roms_gpu_zslice_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
     L.roms_gpu_time_calc_zslice.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_extract_begin.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+    L.roms_gpu_extract_angler.argtypes = [ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_extract_add_object.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_long, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p]
+    L.roms_gpu_extract_objects_file.argtypes = [ctypes.c_char_p]
+    L.roms_gpu_calc_extract.argtypes = [P(Tlev)]
+    L.roms_gpu_wrt_extract.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, P(Tlev)]
+    L.roms_gpu_extract_state.argtypes = [P(ctypes.c_int)] * 5
+    L.roms_gpu_extract_object_info.argtypes = [ctypes.c_int] + [P(ctypes.c_int)] * 5
+    L.roms_gpu_extract_object_coef.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+    L.roms_gpu_extract_child_cs.argtypes = [ctypes.c_void_p]
+    L.roms_gpu_extract_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_time_calc_extract.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_extract_locate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                          ctypes.c_void_p, ctypes.c_void_p, P(ctypes.c_int), P(ctypes.c_int)]
     _lib = L
     return L
 
@@ -224,6 +239,24 @@ AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=
 # ROMS_ZSL_* of include/roms_gpu.h (zslice_output.opt wrt_*_zsl switches)
 ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
 ZSL_MAXDEP = 32
+# ROMS_EXT_* of include/roms_gpu.h (the output_vars of an extraction object); up, vp, w, bgc are reported, not produced
+EXT = dict(zeta=1, ubar=2, vbar=4, u=8, v=16, temp=32, salt=64, up=128, vp=256, w=512, bgc=1024)
+EXT_3D = ("u", "v", "temp", "salt")
+
+
+def extract_locate(nx, ny, iSW_corn, jSW_corn, ipos, jpos):
+    """find_local_points of extract_data.F (host-only call): (start_idx, np) of the first contiguous run of
+    points inside the subdomain, start_idx 1-based; (0, 0) when there is none."""
+    L = load_library()
+    i = np.ascontiguousarray(ipos, dtype=np.float64).ravel()
+    j = np.ascontiguousarray(jpos, dtype=np.float64).ravel()
+    if i.size != j.size:
+        raise ValueError("extract_locate: ipos and jpos differ in length")
+    s, n = ctypes.c_int(), ctypes.c_int()
+    if L.roms_gpu_extract_locate(nx, ny, iSW_corn, jSW_corn, i.size, i.ctypes.data, j.ctypes.data, ctypes.byref(s),
+                                 ctypes.byref(n)) != 0:
+        raise ValueError("bad extract_locate arguments")
+    return s.value, n.value
 # enum roms_routine of include/roms_gpu.h
 ROUTINES = ("rho_eos", "set_HUV", "omega", "prsgrd", "pre_step3d", "set_HUV1", "step3d_uv1", "visc3d", "step2d",
             "step3d_uv2", "step3d_t", "t3dmix", "lmd_vmix",
@@ -768,6 +801,88 @@ class Model:
         self._chk(self.L.roms_gpu_zslice_copy_out(bit, 1 if q is None else q, a.ctypes.data, a.size),
                   "zslice_copy_out " + name)
         return a.reshape((ndep,) + self.shape2)
+
+    # ---- child-boundary extraction (do_extract_data, extract_data.F) ----
+    def extract_begin(self, N_chd, theta_s_chd, theta_b_chd, hc_chd, angler=None):
+        """Clear every extraction object and set the child's vertical grid (the remap is used unless all four
+        equal the parent's); angler: the grid angle as (Mm+4, Lm+4), default 0."""
+        self._chk(self.L.roms_gpu_extract_begin(N_chd, theta_s_chd, theta_b_chd, hc_chd), "extract_begin")
+        if angler is not None:
+            a = np.ascontiguousarray(angler, dtype=np.float64).ravel()
+            self._chk(self.L.roms_gpu_extract_angler(a.ctypes.data, a.size), "extract_angler")
+
+    def extract_add(self, name, ipos, jpos, output_vars, ang=None, dname=None):
+        """Add one object: fractional positions in absolute index space, `ang` per point for a vector object.
+        Returns its 1-based index; names of requested but unsupported variables are in extract_info()."""
+        i = np.ascontiguousarray(ipos, dtype=np.float64).ravel()
+        j = np.ascontiguousarray(jpos, dtype=np.float64).ravel()
+        a = None if ang is None else np.ascontiguousarray(ang, dtype=np.float64).ravel()
+        if i.size != j.size or (a is not None and a.size != i.size):
+            raise ValueError("extract_add: ipos, jpos and ang differ in length")
+        self._chk(self.L.roms_gpu_extract_add_object(name.encode(), (dname or "n_" + name).encode(), i.size, i.ctypes.data,
+                                                     j.ctypes.data, None if a is None else a.ctypes.data,
+                                                     output_vars.encode()), "extract_add " + name)
+        return self.extract_state()[0]
+
+    def extract_objects_file(self, path):
+        """Add every object of the reference's objects netCDF file; returns their number so far."""
+        self._chk(self.L.roms_gpu_extract_objects_file(path.encode()), "extract_objects_file")
+        return self.extract_state()[0]
+
+    def calc_extract(self):
+        """One sample: zeta, ubar, vbar(knew), u, v, temp, salt(nstp) at every object's points."""
+        self._chk(self.L.roms_gpu_calc_extract(ctypes.byref(self.t)), "calc_extract")
+
+    def wrt_extract(self, path, rec, total_rec, time):
+        """Sample, then write record rec of this rank's extraction file."""
+        self._chk(self.L.roms_gpu_wrt_extract(path.encode(), rec, total_rec, time, ctypes.byref(self.t)), "wrt_extract")
+
+    def extract_state(self):
+        """(nobj, mismatch, N_chd, np_total, need_huv)."""
+        v = [ctypes.c_int() for _ in range(5)]
+        self._chk(self.L.roms_gpu_extract_state(*[ctypes.byref(x) for x in v]), "extract_state")
+        return v[0].value, bool(v[1].value), v[2].value, v[3].value, bool(v[4].value)
+
+    def extract_info(self, iobj):
+        """dict(np, start_idx, vars, unsupported, scalar) of object iobj; vars/unsupported as name tuples."""
+        v = [ctypes.c_int() for _ in range(5)]
+        self._chk(self.L.roms_gpu_extract_object_info(iobj, *[ctypes.byref(x) for x in v]), "extract_object_info")
+        names = lambda m: tuple(k for k, b in EXT.items() if m & b)
+        return dict(np=v[0].value, start_idx=v[1].value, vars=names(v[2].value), unsupported=names(v[3].value),
+                    scalar=bool(v[4].value))
+
+    def extract_coef(self, iobj, grid):
+        """(ip, jp, coef(4, np), cosa, sina) of object iobj on grid "r", "u" or "v"."""
+        n = self.extract_info(iobj)["np"]
+        ip, jp = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        cf, ca, sa = np.zeros((4, n)), np.zeros(n), np.zeros(n)
+        self._chk(self.L.roms_gpu_extract_object_coef(iobj, "ruv".index(grid), ip.ctypes.data, jp.ctypes.data,
+                                                      cf.ctypes.data, ca.ctypes.data, sa.ctypes.data), "extract_object_coef")
+        return ip, jp, cf, ca, sa
+
+    def extract_child_cs(self):
+        """Cs_w_chd(0:N_chd) of set_chd_scoord."""
+        a = np.zeros(self.extract_state()[2] + 1)
+        self._chk(self.L.roms_gpu_extract_child_cs(a.ctypes.data), "extract_child_cs")
+        return a
+
+    def extract(self, iobj, name):
+        """Variable `name` of object iobj from the last sample: (levels, np) for u, v, temp, salt (levels = N_chd
+        with the remap, else N), (np,) for zeta, ubar, vbar."""
+        if name not in EXT:
+            raise ValueError("extract: unknown variable %s" % name)
+        _, mismatch, nchd, _, _ = self.extract_state()
+        n = self.extract_info(iobj)["np"]
+        rows = (nchd if mismatch else self.N) if name in EXT_3D else 1
+        a = np.empty(rows * n, dtype=np.float64)
+        self._chk(self.L.roms_gpu_extract_copy_out(iobj, EXT[name], a.ctypes.data, a.size), "extract_copy_out " + name)
+        return a.reshape(rows, n) if name in EXT_3D else a
+
+    def time_calc_extract(self, n):
+        """(ms of n interpolation launches, ms of n remap launches)."""
+        ms = (ctypes.c_double * 2)()
+        self._chk(self.L.roms_gpu_time_calc_extract(n, ctypes.byref(self.t), ms), "time_calc_extract")
+        return ms[0], ms[1]
 
     def get_init(self, path, req_rec, tindx):
         """get_init(req_rec, tindx); returns 0 (read) or 1 (exact restart not possible)."""
