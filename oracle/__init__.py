@@ -3,7 +3,12 @@
 ctypes binding of oracle/liboracle.so (plain-C restatement, see
 roms_oracle.h).  Only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg may import this package.  Parity pinned against the
-reference golden log tests/Filament/benchmark.result_github_gnu.
+reference golden log tests/Filament/benchmark.result_github_gnu; the
+open-boundary routines, set_nudgcof and the bulk fluxes against the reference
+routines themselves, compiled by oracle/ref/build_ref.sh (oracle.ref,
+tests/test_ref_pin_obc.py, tests/test_ref_pin_bulk.py).  Still unpinned: the
+CURVGRID momentum terms, tides and forcing interpolation, ADV_ISONEUTRAL,
+LMD_DDMIX.
 """
 import ctypes
 import os
@@ -79,6 +84,12 @@ def lib():
                    "or_visc3d", "or_step2d", "or_step3d_uv2", "or_step3d_t", "or_t3dmix", "or_set_depth",
                    "or_diag", "or_swr_frac", "or_bulk_flux"):
             getattr(L, fn).argtypes = [ctypes.c_void_p]
+        # the boundary routines and the sponge, called one by one by tests/test_ref_pin_obc.py
+        for fn in ("or_u2dbc", "or_v2dbc", "or_u3dbc", "or_v3dbc", "or_set_nudgcof"):
+            getattr(L, fn).argtypes = [ctypes.c_void_p]
+        L.or_zetabc.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        L.or_t3dbc.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.or_scalars.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         L.or_rho_eos.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.or_lmd_vmix.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.or_set_iif.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -182,6 +193,12 @@ class Oracle:
 
     def nfast(self):
         return self.L.or_nfast(self.h)
+
+    def scalars(self):
+        """dt, dtfast, g, gamma2, rho0 as the routines read them."""
+        out = (ctypes.c_double * 5)()
+        self.L.or_scalars(self.h, out)
+        return dict(zip(("dt", "dtfast", "g", "gamma2", "rho0"), out))
 
     def weights(self):
         p = self.L.or_weights(self.h)

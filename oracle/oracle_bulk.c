@@ -7,7 +7,9 @@
  * and the stability functions bulk_psiu / bulk_psit (bulk_frc.F:916-1036).
  * Inputs: uwnd, vwnd, tair, qair (Q), prate, swrad (short-wave data in W/m2,
  * read into srflx by set_frc_data in the reference), lwrad; t, u, v at nrhs.
- * Without QCORRECTION / SFLX_CORR / TAU_CORRECTION / SEA_ICE_NOFLUX.
+ * Without QCORRECTION / SFLX_CORR / TAU_CORRECTION.  SEA_ICE_NOFLUX is always
+ * on: set_global_definitions.h:470 defines it for every case.
+ * Pinned against the reference routine itself by tests/test_ref_pin_bulk.py.
  */
 #include <math.h>
 
@@ -145,6 +147,12 @@ void or_bulk_flux(or_state *S) {
       const double aer = rhoAir * wspd0 * rho0i, cer = Cd;
       A2(S->sustr_r, i, j) = aer * cer * uw * A2(S->rmask, i, j);
       A2(S->svstr_r, i, j) = aer * cer * vw * A2(S->rmask, i, j);
+      /* SEA_ICE_NOFLUX (bulk_frc.F:789-796): no heat flux into water at the
+         freezing point, nor short-wave where LMD_KPP would absorb it */
+      if (TT(i, j, N, nrhs, 1) <= -1.8) {
+        A2(S->stflx, i, j) = 0.;
+        if (S->c.lmd) A2(S->srflx, i, j) = 0.;
+      }
     }
   /* surface-current feedback and rho -> u, v points (bulk_frc.F:823-910) */
   const double Wspd_min = 3., stau_ref = -0.0027, cfb_slope = -0.0029, cfb_offset = 0.008;

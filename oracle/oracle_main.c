@@ -900,6 +900,9 @@ void or_set_tindex(or_state *S, const int in[6]) {
   S->iic = in[0]; S->kstp = in[1]; S->knew = in[2]; S->nstp = in[3]; S->nrhs = in[4]; S->nnew = in[5];
 }
 void or_set_iif(or_state *S, int iif) { S->iif = iif; }
+void or_scalars(const or_state *S, double out[5]) {
+  out[0] = S->dt; out[1] = S->dtfast; out[2] = S->g; out[3] = S->gamma2; out[4] = S->rho0;
+}
 
 double *or_field(or_state *S, const char *name, size_t *count) {
   struct { const char *n; double *p; size_t c; } tab[] = {

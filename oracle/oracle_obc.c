@@ -17,6 +17,8 @@
  * the OBC_M2ORLANSKI branch (u2dbc_im.F:270-273, v2dbc_im.F:273-276); the
  * eastern and northern tracer radiation reads the interior t(nnew)
  * (t3dbc_im.F:133,276) where the western and southern read t(nstp).
+ * Pinned bitwise against the reference routines themselves by
+ * tests/test_ref_pin_obc.py (oracle/ref/build_ref.sh compiles them).
  */
 #include "oracle_core.h"
 

@@ -101,6 +101,8 @@ void or_bulk_flux(or_state *S);   /* calc_all_bulk_forces at nrhs (oracle_bulk.c
 void or_diag(or_state *S);
 void or_set_tindex(or_state *S, const int in[6]);
 void or_set_iif(or_state *S, int iif);
+/* the scalars the boundary routines read: dt dtfast g gamma2 rho0 */
+void or_scalars(const or_state *S, double out[5]);
 /* set_river_frc: new riv_vol(nriv), riv_trc(nriv,NT) (faces kept) */
 void or_set_river(or_state *S, int nriv, const double *vol, const double *trc);
 void or_set_ub(or_state *S, const double *w, const double *e, const double *s, const double *n);

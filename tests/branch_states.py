@@ -27,6 +27,10 @@ tests/test_gpu_branches.py runs the HIP kernels on the same states.
                  inside the top cell
   kpp_swr_state  well-mixed columns under cooling and wind: the boundary
                  layer reaches levels where swr_frac is exactly zero
+  bulk_state     the bulk fluxes under the analytic atmosphere and under one
+                 that reaches the other arms of calc_all_bulk_forces: stable
+                 and unstable air, calm, every Charnock range, no rain, a
+                 coast, water at and below the -1.8 degC of SEA_ICE_NOFLUX
 """
 import numpy as np
 
@@ -132,17 +136,19 @@ FLATHER_NDTFAST = 4
 FLATHER_CELL = 2.3e3
 
 
-def flather_cfg(obc, ndtfast=FLATHER_NDTFAST):
-    return obc_cfg(obc=obc, curv=1, ndtfast=ndtfast, sizex=FLATHER_CELL * 48, sizey=FLATHER_CELL * 40)
+def flather_cfg(obc, ndtfast=FLATHER_NDTFAST, LLm=48, MMm=40, N=12):
+    return obc_cfg(obc=obc, curv=1, ndtfast=ndtfast, LLm=LLm, MMm=MMm, N=N, sizex=FLATHER_CELL * LLm,
+                   sizey=FLATHER_CELL * MMm)
 
 
-def flather_state(obc):
+def flather_state(obc, **size):
     """Three steps at ndtfast = 30, then every field handed to a model of the
     same grid with ndtfast = 4: one state for single step2d calls, not a run.
     The indices returned are those after the three steps; step2d's callers
-    advance kstp / knew themselves (fast_indices)."""
-    donor = _started(flather_cfg(obc, ndtfast=30))
-    cfg = flather_cfg(obc)
+    advance kstp / knew themselves (fast_indices).  size: LLm, MMm, N other
+    than 48 x 40 x 12, the cells staying 2.3 km."""
+    donor = _started(flather_cfg(obc, ndtfast=30, **size))
+    cfg = flather_cfg(obc, **size)
     o = oracle.Oracle(cfg)
     o.init()
     for name in romsgpu.FIELDS:
@@ -295,3 +301,73 @@ def kpp_base(o, cfg):
     for k in range(N - 1, 0, -1):
         kbls = np.where(zw[k][I] > zw[N][I] - hbl, k, kbls)
     return kbls, np.take_along_axis(sw[I], (kbls - 1)[None], 0)[0]
+
+
+# ------------------------------------------------------------------ bulk ----
+BULK_SIZE = dict(LLm=24, MMm=20, N=6)        # the grid of the reference libraries (oracle/ref/build_ref.sh)
+BULK_ATM = ("uwnd", "vwnd", "tair", "qair", "prate", "lwrad", "swrad")
+BULK_OUT = ("sustr", "svstr", "sustr_r", "svstr_r", "stflx", "swflx", "srflx")
+T_ICE = -1.8                                  # bulk_frc.F:790
+
+
+def bulk_state(kind, mode="nstp"):
+    """The closed basin with BULK_FRC and KPP after four steps, nrhs = nstp
+    or 3.  kind 'analytic': the atmosphere of or_ana_forces as it stands.
+    kind 'arms': air 6 degC colder to 6 degC warmer than the sea across the
+    basin, dry to humid northwards, no wind at all over the southern
+    quarter and up to 26 m/s in the north, rain over the eastern half only,
+    a block of land, and a patch of surface water at -1.9 degC with one
+    cell at -1.8 exactly."""
+    from test_gpu_bulk import bulk_cfg
+    cfg = bulk_cfg(**BULK_SIZE)
+    o = _started(cfg, steps=4)
+    tix = o.tindex()
+    tix[4] = tix[3] if mode == "nstp" else 3
+    o.set_tindex(tix)
+    if kind == "analytic":
+        return cfg, o, tix
+    ny2, nx2, N = cfg.MMm + 4, cfg.LLm + 4, cfg.N
+    fy, fx = np.meshgrid(np.arange(ny2) / (ny2 - 1.0), np.arange(nx2) / (nx2 - 1.0), indexing="ij")
+    t = o.field("t").reshape(cfg.NT, 3, N, ny2, nx2)
+    t[0, :, N - 1, 14:17, 18:21] = -1.9
+    t[0, :, N - 1, 15, 19] = T_ICE
+    rm = o.field("rmask")[0]
+    rm[8:12, 10:14] = 0.0
+    o.field("umask")[0][:, 1:] = rm[:, 1:] * rm[:, :-1]
+    o.field("vmask")[0][1:, :] = rm[1:, :] * rm[:-1, :]
+    windy = fy > 0.25
+    sst = t[0, tix[4] - 1, N - 1]
+    o.field("tair")[0][...] = sst + 6.0 * np.cos(2.0 * np.pi * fx)
+    o.field("qair")[0][...] = 0.004 + 0.012 * fy
+    o.field("uwnd")[0][...] = np.where(windy, 26.0 * fy, 0.0)
+    o.field("vwnd")[0][...] = np.where(windy, 3.0 * np.sin(2.0 * np.pi * fx), 0.0)
+    o.field("prate")[0][...] = np.where(fx > 0.5, 0.6, 0.0)
+    o.field("lwrad")[0][...] = 280.0 + 80.0 * fy
+    o.field("swrad")[0][...] = 200.0 * fx
+    return cfg, o, tix
+
+
+def bulk_arms(o, cfg, tix):
+    """The data-dependent arms of calc_all_bulk_forces that follow from its
+    inputs alone, over the extended bounds 0:Lm+1 x 0:Mm+1: the sign of the
+    bulk Richardson number (bulk_frc.F:600-606), the Charnock ranges of
+    delW (:626-632), the current-feedback threshold (:844), rain, land,
+    and the sea-ice test (:790)."""
+    N, ny2, nx2 = cfg.N, cfg.MMm + 4, cfg.LLm + 4
+    E = (slice(1, ny2 - 1), slice(1, nx2 - 1))
+    f = lambda n: o.field(n)[0][E]
+    sst = o.field("t").reshape(cfg.NT, 3, N, ny2, nx2)[0, tix[4] - 1, N - 1][E]
+    tair, q = f("tair"), f("qair")
+    wspd = np.sqrt(f("uwnd") * f("uwnd") + f("vwnd") * f("vwnd"))
+    patm = 1010.0
+    es = (1.0007 + 3.46e-6 * patm) * 6.1121 * np.exp(17.502 * sst / (240.97 + sst)) * 0.98
+    qsea = 0.62197 * (es / (patm - 0.378 * es))
+    buoy = (sst - tair) + 0.61 * (tair + 273.16) * (qsea - q)      # Ri = -g*ZW*buoy/(TairK*delW**2)
+    delw = np.sqrt(wspd * wspd + 0.5 * 0.5)
+    wet = f("rmask") == 1.0
+    return {"unstable (Ri < 0)": buoy > 0.0, "stable (Ri >= 0)": buoy <= 0.0,
+            "calm and unstable": (wspd == 0.0) & (buoy > 0.0), "calm and stable": (wspd == 0.0) & (buoy <= 0.0),
+            "delW <= 10": delw <= 10.0, "10 < delW <= 18": (delw > 10.0) & (delw <= 18.0), "delW > 18": delw > 18.0,
+            "wspd > 3 (current feedback)": wspd > 3.0, "wspd <= 3": wspd <= 3.0,
+            "rain": f("prate") > 0.0, "no rain": f("prate") == 0.0, "wet": wet, "land": ~wet,
+            "ice: t < -1.8": wet & (sst < T_ICE), "ice: t = -1.8": wet & (sst == T_ICE), "no ice": wet & (sst > T_ICE)}

@@ -7,14 +7,23 @@ The reference reads the atmosphere from netCDF; the C4 stand-in (SURVEY.md
 8(d)) is a synthetic analytic atmosphere over the closed basin (westerly
 jet, air a few degC off the sea surface, humid, light rain), set identically
 by the oracle (oracle_main.c or_ana_forces) and the host (host_init.cpp).
-Parity unpinned against the reference itself: no reference test or golden
-log exercises BULK_FRC, so the HIP path is held to the oracle's restatement
-(oracle/oracle_bulk.c, bulk_frc.F line by line):
-  * the fluxes after init and after one call from a mid-run state (1e-12
-    relative; the bulk formulae carry exp/log/sqrt/pow, an ulp apart
-    between device libm and glibc);
+Pinned against the reference itself: no reference test or golden log
+exercises BULK_FRC, but bulk_frc.F compiles unchanged beside stand-ins for
+its I/O modules (oracle/ref/build_ref.sh), and tests/test_ref_pin_bulk.py
+holds the oracle's restatement (oracle/oracle_bulk.c) to that routine within
+8 ulp on two atmospheres that between them take every arm.  Here:
+  * the fluxes after init and after one call from a mid-run state against
+    the oracle (1e-12 relative; the bulk formulae carry exp/log/sqrt/pow,
+    an ulp apart between device libm and glibc);
+  * Model.bulk_flux() against the reference routine directly, on the same
+    two atmospheres, where the library was built (it travels with
+    oracle/_ref/; nothing is read from the reference tree);
   * a 40-step basin run with KPP: diag norms and field RMS (north_star 1e-10).
+Still unpinned: the time interpolation of the forcing records (set_frc_data
+reads netCDF), which the oracle restates in or_frc_record / frc_interp.
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -138,3 +147,47 @@ def test_bulk_rain_heat_uses_air_temperature():
     dT = (t1[0, -1] - t0[0, -1])[2:-2, 2:-2]
     assert np.all(dT[wet] != 0.0)
     assert np.array_equal(t1[1], t0[1])   # salinity does not see tair
+
+
+@pytest.mark.parametrize("kind,mode", [("analytic", "nstp"), ("arms", "corr")])
+def test_bulk_flux_matches_reference_routine(kind, mode):
+    """Model.bulk_flux() against set_bulk_frc of the reference itself, at the
+    library's 24 x 20 x 6, on the analytic atmosphere and on the one that
+    takes the other arms (stable air, calm, strong wind, no rain, land, water
+    at and below -1.8 degC: branch_states.bulk_state).  Whole arrays, ghost
+    points included; srflx on the extended bounds the routine works on.
+    The sea-ice arm failed here before k_bulk.hip had it: stflx and srflx
+    were not zeroed where t(N) <= -1.8."""
+    import branch_states as bs
+    import oracle.ref as ref
+    if not os.path.exists(ref.lib_path(ref.BULK)):
+        pytest.skip("oracle/_ref/libref_bulk.so is built only where the reference tree is")
+    cfg, o, tix = bs.bulk_state(kind, mode)
+    arms = bs.bulk_arms(o, cfg, tix)
+    if kind == "arms":
+        assert all(bool(np.any(v)) for v in arms.values()), [k for k, v in arms.items() if not np.any(v)]
+    for n in bs.BULK_OUT:
+        o.field(n)[...] = 0.125
+    r = ref.RefLib(ref.BULK)
+    r.load(o, any_sides=True)
+    want = r.bulk({n: o.field(n).copy() for n in bs.BULK_ATM}, {n: o.field(n).copy() for n in bs.BULK_OUT})
+    m = romsgpu.Model.from_case(cfg.case_id, cfg.LLm, cfg.MMm, cfg.N, cfg.NT, salinity=True, nonlin_eos=True,
+                                dt=cfg.dt, ndtfast=cfg.ndtfast, sizex=cfg.sizex, sizey=cfg.sizey, lmd=cfg.lmd,
+                                bulk_frc=True)
+    copy_state(o, m)
+    m.set_tindex(*tix, iif=1, nfast=o.nfast())
+    m.bulk_flux()
+    m.sync()
+    cut = lambda n, a: a[..., 1:-1, 1:-1] if n == "srflx" else a
+    errs = {}
+    for n in bs.BULK_OUT:
+        got = m.get(n)
+        a, b = cut(n, got), cut(n, want[n].reshape(got.shape))
+        errs[n] = float(np.max(np.abs(a - b))) / max(float(np.max(np.abs(b))), 1e-300)
+    print(kind, mode, errs)
+    bad = {n: e for n, e in errs.items() if not e <= RTOL_ROUTINE}
+    assert not bad, bad
+    if kind == "arms":
+        ice = arms["ice: t < -1.8"] | arms["ice: t = -1.8"]
+        assert np.all(m.get("stflx")[0][1:-1, 1:-1][ice] == 0.0) and np.all(m.get("srflx")[0][1:-1, 1:-1][ice] == 0.0)
+    m.close()

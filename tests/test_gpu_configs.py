@@ -22,9 +22,12 @@ switch variants.
   Switch variants: LMD_RIMIX / LMD_CONVEC / LMD_NONLOCAL individually off,
   UV_ADV and UV_COR off (compute_horiz_rhs_uv_terms.h, compute_vert_rhs_uv_terms.h).
 
-The OBC/SPONGE/CURVGRID branches of the oracle have no runnable golden log
-offline (test_gpu_obc.py): "parity unpinned" there; everything else is
-pinned through the Filament / Pipes_ana goldens (test_oracle_golden.py).
+The OBC, SPONGE(_TUNE) and BULK_FRC branches of the oracle have no runnable
+golden log offline; they are pinned routine by routine to the reference's own
+code compiled beside stand-in modules (test_ref_pin_obc.py,
+test_ref_pin_bulk.py).  The CURVGRID momentum terms remain "parity unpinned"
+(test_gpu_obc.py); everything else is pinned through the Filament / Pipes_ana
+goldens (test_oracle_golden.py).
 """
 import os
 

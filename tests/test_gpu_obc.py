@@ -8,10 +8,17 @@ The case is the synthetic basin with all four edges open, an island and
 analytic time-independent boundary data (Iceland switch set,
 Examples/Iceland/Iceland_parent/cppdefs.opt; the real Iceland inputs are not
 available offline).  The oracle's open-boundary restatement
-(oracle/oracle_obc.c) has no golden log of its own -- the reference's OBC
-tests need netCDF inputs fetched from GitHub -- so this parity is GPU vs
-oracle only ("parity unpinned" for the OBC branches; the closed-wall branches
-of the same routines stay pinned by the Filament / Pipes_ana goldens).
+(oracle/oracle_obc.c) and its sponge (or_set_nudgcof) are pinned to the
+reference routines themselves: zetabc, u2dbc_im, v2dbc_im, u3dbc_im, v3dbc_im,
+t3dbc_im and set_nudgcof compile unchanged beside stand-in modules
+(oracle/ref/build_ref.sh), and tests/test_ref_pin_obc.py holds the oracle to
+them bitwise for open sides 15, 5 and 10, predictor and corrector, ub_tune
+off and on, on states that take every data-dependent arm on every open side.
+So parity here, GPU vs oracle, means GPU vs reference for these routines.
+The CURVGRID momentum terms (test_curvgrid_momentum_rhs_parity) stay "parity
+unpinned": they sit in the r.h.s. routines, which need more of the reference
+than the stand-ins give.  The closed-wall branches stay pinned by the
+Filament / Pipes_ana goldens as before.
 Tolerances as in test_gpu_parity: 1e-12 relative per routine (sqrt in
 Flather's phase speed may differ by an ulp), field RMS < 1e-10 per run.
 """

@@ -10,10 +10,10 @@
 // (downward long-wave, W/m2); the model's surface t(N,nrhs), u,v(N,nrhs).
 // Outputs: srflx [degC m/s], stflx(:,:,itemp), swflx, sustr_r, svstr_r
 // (rho points, used by lmd_kpp.F:174 for u*) and sustr, svstr (u/v points).
-// Without QCORRECTION / SFLX_CORR / TAU_CORRECTION / SEA_ICE_NOFLUX /
-// DIURNAL_SRFLUX (not defined by Examples/Iceland; stflx(isalt) is left as
-// the host set it).  One thread per rho point; FP64 with the reference's
-// operation order.
+// Without QCORRECTION / SFLX_CORR / TAU_CORRECTION / DIURNAL_SRFLUX (not
+// defined by Examples/Iceland; stflx(isalt) is left as the host set it).
+// SEA_ICE_NOFLUX is on, as set_global_definitions.h:470 defines it for every
+// case.  One thread per rho point; FP64 with the reference's operation order.
 #include "roms_dev.h"
 
 namespace roms {
@@ -159,6 +159,12 @@ __global__ void __launch_bounds__(256) k_bulk_flux(Dev d, Range R, int nrhs) {
   const double aer = rhoAir * wspd0 * rho0i, cer = Cd;
   F.sustr_r[ij] = aer * cer * uw * rm;
   F.svstr_r[ij] = aer * cer * vw * rm;
+  // SEA_ICE_NOFLUX (bulk_frc.F:789-796): no heat flux into water at the freezing
+  // point, nor short-wave where LMD_KPP would absorb it
+  if (TseaC <= -1.8) {
+    F.stflx[ij] = 0.;
+    if (P.lmd) F.srflx[ij] = 0.;
+  }
 }
 
 // ---- surface-current feedback on the rho-point stresses (bulk_frc.F:823-895):
