@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 27 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 28 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! extraction variables (ROMS_EXT_*); UP, VP, W, BGC are parsed and reported, not produced
   integer(c_int), parameter :: ROMS_EXT_ZETA = 1, ROMS_EXT_UBAR = 2, ROMS_EXT_VBAR = 4, ROMS_EXT_U = 8, &
                                ROMS_EXT_V = 16, ROMS_EXT_TEMP = 32, ROMS_EXT_SALT = 64, ROMS_EXT_UP = 128, &
@@ -133,6 +133,11 @@ module roms_gpu_mod
     end function
     ! ROMS_GPU_T_PAIR mask + 256 * (Akt(isalt) known equal to Akt(itemp)); pair-form launches of pre_step3d, step3d_t
     integer(c_int) function roms_gpu_tracer_pair(launches) bind(c)
+      import :: c_int, c_long
+      integer(c_long), intent(out) :: launches(2)
+    end function
+    ! ROMS_GPU_LEAN_ST mask; pre_step3d launches that left the u, v(indx) store out, lmd_vmix launches that left Akt(isalt) out
+    integer(c_int) function roms_gpu_lean_stores(launches) bind(c)
       import :: c_int, c_long
       integer(c_long), intent(out) :: launches(2)
     end function

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 27
+#define ROMS_GPU_ABI_VERSION 28
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -372,6 +372,30 @@ int roms_gpu_vgrid_check(long out[3]);
  * pre_step3d and of step3d_t this host thread enqueued since init (a replayed
  * graph counts those of its capture).                                        */
 int roms_gpu_tracer_pair(long launches[2]);
+/* Stores of a whole step that nothing in the step reads (ABI 28).
+ * ROMS_GPU_LEAN_ST (read at init; a mask, default 3, 0 for every store):
+ *   1  pre_step3d's u, v(indx) = Hz*u(nstp): on the buffer segment path
+ *      (N = 88..104, UV_ADV) roms_gpu_step's predictor does not store them and
+ *      its step3d_uv1, their one reader, forms each value again from the same
+ *      Hz and u(nstp) with the same expression, so every field keeps its bits
+ *      and after the step u, v(indx) hold what step3d_uv1 left there, as before.
+ *      The routine entries roms_gpu_pre_step3d and roms_gpu_step3d_uv1 always
+ *      store and load u, v(indx).
+ *   2  Akt(isalt): where lmd_vmix leaves it bit for bit Akt(itemp) (no
+ *      LMD_DDMIX, equal Akt_bak) and both tracer solvers of the step are the
+ *      pair kernels (ROMS_GPU_T_PAIR = 3, NT = 2, buffer segment path, no
+ *      ADV_ISONEUTRAL), roms_gpu_step's lmd_vmix neither forms, stores nor
+ *      exchanges it.  The library copies Akt(itemp) over it, halos and edge
+ *      points included, before anything reads it: roms_gpu_copy_out and
+ *      roms_gpu_download of Akt, roms_gpu_calc_avg and roms_gpu_wrt_his with
+ *      ROMS_WRT_AKS, roms_gpu_pre_step3d and roms_gpu_step3d_t.  The host sees
+ *      Akt as before.  A host write of Akt is kept as written; roms_gpu_lmd_vmix
+ *      as a routine always stores both slots.
+ * roms_gpu_lean_stores returns the mask, negative before init; launches[0],
+ * launches[1] (if not NULL) get the pre_step3d and the lmd_vmix launches this
+ * host thread enqueued since init that left their store out (a replayed graph
+ * counts those of its capture).                                             */
+int roms_gpu_lean_stores(long launches[2]);
 /* The horizontal tracer kernels of pre_step3d and step3d_t as level walks
  * (ABI 23).  With two tracers the kernels of ROMS_GPU_T_HSTG (read at init; a
  * mask, default 7 with the segment solvers and 2 with the column solvers of

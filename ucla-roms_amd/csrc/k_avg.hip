@@ -153,6 +153,8 @@ int avg_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) 
   const Bounds& b = S.d->b;
   const long ok = (long)(t.knew - 1) * b.n2, on = (long)(t.nstp - 1) * b.n3;
   const dim3 grid(avg_blocks(A.nmax), (unsigned)A.fields.size());
+  // AKs samples Akt(isalt), which whole steps may leave unformed (shim_akt_sync)
+  if ((A.v.mask & ROMS_WRT_AKS) && shim_akt_sync() != hipSuccess) return -3;
   if (coef == 1.0) hipLaunchKernelGGL(k_calc_avg<true>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
   else hipLaunchKernelGGL(k_calc_avg<false>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
   return hipGetLastError() == hipSuccess ? 0 : -3;

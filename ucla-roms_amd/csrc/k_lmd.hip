@@ -575,7 +575,12 @@ __global__ void __launch_bounds__(64, kpp_ext_waves(PF)) k_kpp_ext(Dev d, Range 
 // the levels too (barriers) and store nothing.  Same values bitwise.
 // VG (Params::vg bit kVgKppInt): z_w from VGrid -- the kbls scan, the levels'
 // z_w, z_w(N), z_w(0), the per-lane z_w at kbls and Hz(1).
-template <bool kDD, int TY = 0, int MW = 1, bool VG = false>   // MW: minimum waves per SIMD (VGPR cap)
+// kOne (Params::lean_st bit kLeanAkt, whole steps only, never with kDD): the
+// one-slot form.  Ks would be Kt bit for bit (equal backgrounds), and the
+// step's tracer solvers read Akt(itemp) for both tracers (the pair kernels),
+// so there is no Ks chain (rs, ss, ns, rsN, its two square roots per level)
+// and no Akt(isalt) store; Kt's expressions are the same.
+template <bool kDD, int TY = 0, int MW = 1, bool VG = false, bool kOne = false>   // MW: minimum waves per SIMD (VGPR cap)
 __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, Range R, EdgeClamp ec, int tind, int nstp,
                                                                    int first, KppConst kc) {
   constexpr bool STG = TY > 0;
@@ -734,7 +739,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       kv = kNuwm;
       kt = kNuws;
     }
-    ks = kt;
+    if constexpr (!kOne) ks = kt;
     const double zwk = VG ? vg.zw1(L.k, L.zw) : L.zw;
     if (dd) ddmix(L.t0, L.t1, L.s0, L.s1, zwk, kt, ks);
     const double dist = zwk - zw0;
@@ -742,7 +747,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       const double mult = sin(0.5 * kPi * (zwk - zw0) / kLturb);
       kv = kv * mult;
       kt = kt * mult;
-      ks = ks * mult;
+      if constexpr (!kOne) ks = ks * mult;
     }
     zwl = zwk;
   };
@@ -768,8 +773,10 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       Kv = sqrt(a * a + q * q);
       a = amp * Kt; q = ws * hbl * cff;
       Kt = sqrt(a * a + q * q);
-      a = amp * Ks;
-      Ks = sqrt(a * a + q * q);
+      if constexpr (!kOne) {
+        a = amp * Ks;
+        Ks = sqrt(a * a + q * q);
+      }
       if (Bfsfc < 0.) gh = -(kc.Cg * ssgm * ((1. - ssgm) * (1. - ssgm)));
     }
     const unsigned ow = (unsigned)k * lv;
@@ -781,15 +788,16 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
       Kv = sqrt(Kv * Kv + q * q);
       q = wsb * bbl * cff1;
       Kt = sqrt(Kt * Kt + q * q);
-      Ks = sqrt(Ks * Ks + q * q);
+      if constexpr (!kOne) Ks = sqrt(Ks * Ks + q * q);
     }
     Akv.st(wet ? Kv : 0., vs, ow);
     AktT.st(wet ? Kt : 0., vs, ow);
-    if (b.nTS > 1) AktS.st(wet ? Ks : 0., vs, ow);
+    if constexpr (!kOne)
+      if (b.nTS > 1) AktS.st(wet ? Ks : 0., vs, ow);
   };
   // bottom-up stream: padding (lmd_vmix.F:359-370) and the in-place ascending
   // 1-2-1 filter Kv(k) = 0.5 Kv(k) + 0.25 Kv(k-1)[filtered] + 0.25 Kv(k+1)[raw] + bak
-  double rv, rt, rs;  // raw level k (rs = rt unless LMD_DDMIX)
+  double rv, rt, rs = 0.;  // raw level k (rs = rt unless LMD_DDMIX; kOne: unused, as ss, ns, rsN)
   // PD levels' loads in flight ahead of the one formed (a ring of RL)
   constexpr int PD = kKppPfd;
   RL La, Lr[PD];
@@ -818,7 +826,7 @@ __global__ void __launch_bounds__(TY > 0 ? kCX * TY : 64, MW) k_kpp_int(Dev d, R
     }
     sv = 0.5 * rv + 0.25 * sv + 0.25 * nv + akv;
     st = 0.5 * rt + 0.25 * st + 0.25 * nt + akt;
-    ss = 0.5 * rs + 0.25 * ss + 0.25 * ns + aks;
+    if constexpr (!kOne) ss = 0.5 * rs + 0.25 * ss + 0.25 * ns + aks;
     finish(k, sv, st, ss, zk);
     rv = rvn; rt = rtn; rs = rsn; zk = zk1;
   }
@@ -850,7 +858,14 @@ void launch_swr_frac(const Dev& d, hipStream_t s) {
   launch_exchange_list(d, s, L);
 }
 
-void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
+// the shapes k_kpp_int's one-slot form is built for: staged Rig windows on 64 x 4 blocks at 2 waves per SIMD (the
+// default), two Akt slots, no LMD_DDMIX
+bool lmd_vmix_one_slot(const Dev& d) {
+  const Params& P = d.p;
+  return P.lmd_rimix && P.kpp_ty != 0 && P.kpp_ty != 2 && P.kpp_ty != 8 && P.kpp_ty != 43 && !P.lmd_ddmix && d.b.nTS == 2;
+}
+
+void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind, bool one_slot) {
   const Bounds& b = d.b;
   // lmd_kpp.F:97-123 (== lmd_vmix.F:105-141): I_EXT_RANGE x J_EXT_RANGE
   Range E;
@@ -897,7 +912,17 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
     else hipLaunchKernelGGL((k_kpp_int<DD, TY, MW, false>), grid, block, 0, s, d, R, ec, tind, t.nstp, first, kc);     \
   } while (0)
   const EdgeClamp ec = edge_clamp(b);
-  if (d.p.kpp_ty && d.p.lmd_rimix) {   // staged Rig windows on 64 x TY column blocks
+  // the one-slot form (lmd_vmix_one_slot): Akt(isalt) is neither formed, stored nor exchanged
+  one_slot = one_slot && lmd_vmix_one_slot(d);
+  if (one_slot) {
+    dim3 g = gridc_of(R);
+    g.y = (g.y + 3) / 4;
+    if (vgi)
+      hipLaunchKernelGGL((k_kpp_int<false, 4, 1, true, true>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
+    else
+      hipLaunchKernelGGL((k_kpp_int<false, 4, 1, false, true>), g, dim3(kCX, 4), 0, s, d, R, ec, tind, t.nstp, first, kc);
+    lean_st_launches(kLeanAkt, 1);
+  } else if (d.p.kpp_ty && d.p.lmd_rimix) {   // staged Rig windows on 64 x TY column blocks
     const int ty = d.p.lmd_ddmix ? 4 : (d.p.kpp_ty == 8 || d.p.kpp_ty == 2) ? d.p.kpp_ty : 4;   // the DDMIX form is instantiated on 64x4 only
     dim3 g = gridc_of(R);
     g.y = (g.y + ty - 1) / ty;
@@ -918,7 +943,7 @@ void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind) {
   L.p[0] = d.f.Akv; L.nlev[0] = b.N + 1;
   L.p[1] = d.f.hbls; L.nlev[1] = 1;
   L.p[2] = d.f.hbbl; L.nlev[2] = 1;
-  L.p[3] = d.f.Akt; L.nlev[3] = (b.N + 1) * b.nTS;
+  L.p[3] = d.f.Akt; L.nlev[3] = (b.N + 1) * (one_slot ? 1 : b.nTS);
   L.n = 4;
   launch_exchange_list(d, s, L);
 }

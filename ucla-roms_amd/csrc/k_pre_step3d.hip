@@ -1043,7 +1043,12 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_seg(Dev d, R
 
 // ---- k_pre_uv_seg<true> with buffer loads/stores (Params::seg_buf): the
 // lane's column and its neighbour, plus the level offset, in VGPR offsets.
-// Same expressions and order: bitwise equal to k_pre_uv_seg<true>. ----
+// Same expressions and order: bitwise equal to k_pre_uv_seg<true>.
+// kStIx = false (Params::lean_st bit kLeanUv, whole steps only): u(indx) =
+// Hz*u(nstp) is neither kept in LDS (no Su: half the dynamic LDS) nor stored;
+// its one reader in a step, k_uv1_segb<true>, forms it again from the same
+// Hz pair and u(nstp). ----
+template <bool kStIx>
 __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, Range R, PreCoef c, int nstp, int nnew,
                                                                          int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
@@ -1067,14 +1072,14 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
   const int nthr = (int)(blockDim.x * blockDim.y * blockDim.z);
   const int tid = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
   double* const Sb = roms_smem + tid;                        // row q-1: cf_stp*u(nstp) + cf_bak*u(indx)
-  double* const Su = roms_smem + (long)(KR - 1) * nthr + tid;  // row q-1: Hz*u(nstp), the new u(indx)
+  double* const Su = roms_smem + (long)(KR - 1) * nthr + tid;  // kStIx, row q-1: Hz*u(nstp), the new u(indx)
   const BufF64 Uix(Uall + (long)(indx - 1) * b.n3), Unew(Uall + (long)(nnew - 1) * b.n3), Hf(F.c2);
   double hf[KR + 1], hfm[KR + 1];   // Hz_fwd(c0-1+q) of the column and of its (i-1) / (j-1) neighbour
   double fl[KR];
   uv_spline_segb<KR>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned L, double h0, double h1, double u) {
     if (q >= 1 && q < KR) {   // cells c0..c0+KR-2 (q is a constant of the unrolled load loop)
       Sb[(q - 1) * nthr] = c.cf_stp * u + c.cf_bak * LD(Uix, vo, L);
-      Su[(q - 1) * nthr] = 0.5 * (h0 + h1) * u;
+      if constexpr (kStIx) Su[(q - 1) * nthr] = 0.5 * (h0 + h1) * u;
     }
   });
   __builtin_amdgcn_sched_barrier(0);   // the viscosity phase's loads stay out of the spline phase
@@ -1132,18 +1137,21 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_pre_uv_segb(Dev d, 
     if (p < n) {
       const unsigned o = lev(c0 + p);
       Unew.st(T.D[p], vs + o, 0u);   // vs = kBufOff stays beyond the extent
-      Uix.st(Su[(p < KR - 1 ? p : KR - 2) * nthr], vs + o, 0u);
+      if constexpr (kStIx) Uix.st(Su[(p < KR - 1 ? p : KR - 2) * nthr], vs + o, 0u);
     }
 }
 
-static size_t pre_uv_seg_lds_bytes(unsigned nthr) {
-  return (size_t)2 * kSegRows * nthr * sizeof(double);
+// Sb and Su; Sb alone without the u(indx) store (k_pre_uv_segb<false>)
+static size_t pre_uv_seg_lds_bytes(unsigned nthr, bool st_ix = true) {
+  return (size_t)(st_ix ? 2 : 1) * kSegRows * nthr * sizeof(double);
 }
 void setup_pre_uv_seg() {
   (void)hipFuncSetAttribute((const void*)k_pre_uv_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax));
+  (void)hipFuncSetAttribute((const void*)k_pre_uv_segb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)pre_uv_seg_lds_bytes(kSegBlock * kSegJMax, false));
 }
 
 void setup_column_kernels_t(size_t bytes);
@@ -1170,6 +1178,14 @@ long t_pair_launches(int bit, long add, bool reset) {
   return c;
 }
 
+static thread_local long lean_st_count[2] = {0, 0};
+long lean_st_launches(int bit, long add, bool reset) {
+  if (reset) lean_st_count[0] = lean_st_count[1] = 0;
+  long& c = lean_st_count[bit == kLeanAkt ? 1 : 0];
+  c += add;
+  return c;
+}
+
 static thread_local long t_hstg_count[3] = {0, 0, 0};
 long t_hstg_launches(int bit, long add, bool reset) {
   if (reset) t_hstg_count[0] = t_hstg_count[1] = t_hstg_count[2] = 0;
@@ -1183,7 +1199,12 @@ double pre_step3d_dtau(const Dev& d, const Tlev& t) {
   return t.iic == t.forw_start ? 0.5 * d.p.dt : d.p.dt * (1.0 - AM3_crv);
 }
 
-void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool hb_done) {
+bool lean_uv_step(const Dev& d, const Tlev& t) {
+  const Params& P = d.p;
+  return (P.lean_st & kLeanUv) && P.colseg && P.seg_buf && P.preuv_lds && P.uv1_lds && P.uv_adv && t.nrhs == t.nstp;
+}
+
+void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool hb_done, bool lean_uv) {
   const Bounds& b = d.b;
   PreCoef c;
   const double AM3_crv = 1.0 / 6.0;
@@ -1259,9 +1280,13 @@ void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
     const dim3 gs = seg_uv_grid(d, RI, d.p.seg_jrows), bs(kCX, seg_waves(b.N), d.p.seg_jrows);
     const bool lds = d.p.preuv_lds && d.p.uv_adv && t.nrhs == t.nstp;
     ktimer_mark(s, kTimedPreUvSeg, 0);
-    if (lds && d.p.seg_buf)
-      hipLaunchKernelGGL(k_pre_uv_segb, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp, t.nnew,
-                         t.nrhs);
+    if (lds && d.p.seg_buf && lean_uv) {
+      hipLaunchKernelGGL(k_pre_uv_segb<false>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z, false), s, d, RI, c,
+                         t.nstp, t.nnew, t.nrhs);
+      lean_st_launches(kLeanUv, 1);
+    } else if (lds && d.p.seg_buf)
+      hipLaunchKernelGGL(k_pre_uv_segb<true>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp,
+                         t.nnew, t.nrhs);
     else if (lds)
       hipLaunchKernelGGL(k_pre_uv_seg<true>, gs, bs, pre_uv_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, RI, c, t.nstp,
                          t.nnew, t.nrhs);

@@ -309,8 +309,14 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_seg(Dev d, Rang
 // ---- k_uv1_seg<true> with buffer loads/stores (Params::seg_buf): the
 // lane's column and its neighbour, plus the level offset, in VGPR offsets
 // (no SGPR pressure).  Same expressions and order: bitwise equal to
-// k_uv1_seg<true>. ----
-__global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Range R, int nnew, int nrhs) {
+// k_uv1_seg<true>.
+// kForm (Params::lean_st bit kLeanUv, whole steps only): the predictor,
+// k_pre_uv_segb<false>, did not store u(nnew) = Hz*u(nstp); each row's base is
+// formed here from the row's Hz pair in LDS and u(nstp), with the predictor's
+// expression and operand order (the same bits: Hz changes only in the fast
+// loop that follows).  One load per row either way. ----
+template <bool kForm>
+__global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Range R, int nnew, int nrhs, int nstp) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
   __shared__ SegXchg X;
   __shared__ double Lf[kSegMaxS][kSegCW * kSegJMax];   // rufrc running sums
@@ -334,6 +340,7 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
   double* const Sh = roms_smem + tid;                             // Hz(c0-1+q) at Sh[q*nthr]
   double* const Shm = roms_smem + (long)(KR + 1) * nthr + tid;    // its neighbour's at Shm[q*nthr]
   const BufF64 Un((dir == 0 ? F.u : F.v) + (long)(nnew - 1) * b.n3);
+  const BufF64 Us((dir == 0 ? F.u : F.v) + (long)((kForm ? nstp : nnew) - 1) * b.n3);   // kForm: u(nstp)
   auto LD = [&](const BufF64& B, unsigned v, unsigned l) { return B.ld(v + l, 0u); };
   double fl[KR];
   uv_spline_segb<KR>(d, sg, X, ij, nrhs, dir, fl, [&](int q, unsigned, double h0, double h1, double) {
@@ -379,7 +386,10 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
     const double b1 = 0.5 * (HZ(p + 1) + HZM(p + 1)) + 0.5 * dt * (rD + rDm) + fcu + fmax0(wcu);
     const double bk = 0.5 * (HZ(p + 1) + HZM(p + 1)) + fcl - fmin0(wcl) + fcu + fmax0(wcu);
     bb = k == 1 ? b1 : bk;
-    const double v = LD(Un, vo, lev(k)) + DC0 * rk[p];
+    double ub;
+    if constexpr (kForm) ub = 0.5 * (HZ(p + 1) + HZM(p + 1)) * LD(Us, vo, lev(k));
+    else ub = LD(Un, vo, lev(k));
+    const double v = ub + DC0 * rk[p];
     dd = k == N ? v + dt * sstr : v;
     fcl = fcu; wcl = wcu;
   });
@@ -420,11 +430,13 @@ void setup_uv1_seg() {
                             (int)((size_t)kSegRows * kSegMaxS * kSegCW * kSegJMax * sizeof(double)));
   (void)hipFuncSetAttribute((const void*)k_uv1_seg<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
-  (void)hipFuncSetAttribute((const void*)k_uv1_segb, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)k_uv1_segb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
+  (void)hipFuncSetAttribute((const void*)k_uv1_segb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
 }
 
-void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done) {
+void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool lean_uv) {
   const Bounds& b = d.b;
   if (!uv_done) launch_uv_horiz(d, s, t.nrhs, 1);
   Range R{b.istr, b.iend, b.jstr, b.jend};
@@ -433,8 +445,12 @@ void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done)
   if (d.p.colseg) {
     const dim3 gs = seg_uv_grid(d, R, d.p.seg_jrows), bs(kCX, seg_waves(b.N), d.p.seg_jrows);
     ktimer_mark(s, kTimedUv1Seg, 0);
-    if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf)
-      hipLaunchKernelGGL(k_uv1_segb, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
+    if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf && lean_uv)   // the predictor left u(nnew) unstored: nstp = 3 - nnew
+      hipLaunchKernelGGL(k_uv1_segb<true>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs,
+                         t.nstp);
+    else if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf)
+      hipLaunchKernelGGL(k_uv1_segb<false>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs,
+                         t.nstp);
     else if (d.p.uv1_lds && d.p.uv_adv)
       hipLaunchKernelGGL(k_uv1_seg<true>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs);
     else

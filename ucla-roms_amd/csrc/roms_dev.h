@@ -105,7 +105,13 @@ struct Params {
   // kpp_pf took the fourth: levels of k_kpp_ext's descending sweep whose loads are in flight ahead of the level formed
   // (ROMS_GPU_KPP_PF, 1..kKppPfMax; 1: the single level ahead; k_lmd.hip)
   int kpp_pf;
-  int reserved_[4];
+  // lean_st took the first of reserved_: stores of a whole step that nothing in the step reads, left out, bitwise
+  // (ROMS_GPU_LEAN_ST bits, default 3, 0: every store): 1 the predictor's u, v(indx) = Hz*u(nstp) (k_pre_uv_segb<false>;
+  // k_uv1_segb<true> forms it again), 2 Akt(isalt) where it is Akt(itemp) bit for bit and the step's tracer solvers
+  // read one slot (k_kpp_int's one-slot form; the shim's akt_stale flag and akt_sync make the slot current for every
+  // other reader).  Whole steps only: the routine entries keep the storing and loading forms.
+  int lean_st;
+  int reserved_[3];
   // ---- sizes and physics masks ----
   int s2d_k;      // fast steps per zeta/ubar/vbar exchange (multi-rank, wide halos of 2*s2d_k; 1: every step)
   int uv2e_nc, uv2e_nf;   // lengths of Fields::uv2e_couple / uv2e_flux
@@ -250,6 +256,9 @@ constexpr int kVg2Default = kVg2All;  // profiles/r10_vgrid_rest_ab.txt
 // Params::t_pair bits (ROMS_GPU_T_PAIR)
 constexpr int kTPairPre = 1, kTPairCor = 2, kTPairAll = 3;
 constexpr int kTPairDefault = kTPairAll;
+// Params::lean_st bits (ROMS_GPU_LEAN_ST)
+constexpr int kLeanUv = 1, kLeanAkt = 2, kLeanAll = 3;
+constexpr int kLeanDefault = kLeanAll;
 // Params::t_hstg bits (ROMS_GPU_T_HSTG)
 constexpr int kTHstgPre = 1, kTHstgCor = 2, kTHstgHz = 4, kTHstgAll = 7;
 constexpr int kTHstgDefault = kTHstgAll, kTHstgDefaultCol = kTHstgCor;   // segment path / column solvers (profiles/r13_tracer_stg_ab.txt)
@@ -512,6 +521,9 @@ int s2d_edge_modes_taken(bool reset = false);
 // per Params::t_pair bit (kTPairPre or kTPairCor; add: count `add` launches
 // of `bit`); a replayed graph counts the launches of its capture only
 long t_pair_launches(int bit, long add = 0, bool reset = false);
+// the same for the launches that left a store out, per Params::lean_st bit
+// (kLeanUv: k_pre_uv_segb<false>)
+long lean_st_launches(int bit, long add = 0, bool reset = false);
 // the same for the staged horizontal tracer kernels, per Params::t_hstg bit
 // (kTHstgPre: k_pre_tracer_stg, kTHstgCor: k_step3d_t_stg, kTHstgHz: the
 // k_pre_tracer_stg launches among them that formed Hz)
@@ -531,8 +543,12 @@ bool launch_tracer_strip(const Dev& d, hipStream_t s, const Range& R, int mode, 
 bool p_in_rho(const Dev& d);   // every rho_eos also forms prsgrd's P (k_vertical.hip)
 bool prsgrd_can_fuse_uv(const Dev& d);
 // hb_done: the interior cells' Hz_bak/Hz_fwd are in c3/c2 already (launch_omega)
-void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false, bool hb_done = false);
-void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false);
+// lean_uv (whole steps, lean_uv_step): k_pre_uv_segb does not store u, v(indx) and k_uv1_segb forms it again; both
+// launches of a step get the same value, and nothing between them may read u, v(indx)
+bool lean_uv_step(const Dev& d, const Tlev& t);   // t: the predictor's indices
+void launch_pre_step3d(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false, bool hb_done = false,
+                       bool lean_uv = false);
+void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done = false, bool lean_uv = false);
 void launch_visc3d(const Dev& d, hipStream_t s, const Tlev& t);
 void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1, const double* w2);
 void launch_step3d_uv2(const Dev& d, hipStream_t s, const Tlev& t);
@@ -556,7 +572,10 @@ void launch_swr_frac(const Dev& d, hipStream_t s);
 constexpr int kKppFcKeepMax = 16;   // most levels above FC(0) in k_kpp_ext's LDS slot: 17 x 64 x 8 B = 8.7 KB per wave
 constexpr int kKppPfMax = 4;        // deepest ring of levels in flight k_kpp_ext is compiled for (Params::kpp_pf)
 constexpr int kKppPfDefault = 3;     // C3: k_kpp_ext 1.12 -> 0.79 ms per launch with 2, 3 or 4, profiles/r15_kpp_ring_prs_vg_ab.txt
-void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind);
+// one_slot (whole steps; taken only where lmd_vmix_one_slot holds): Akt(isalt), bit for bit Akt(itemp) there, is
+// neither formed, stored nor exchanged -- the caller answers for nothing reading it before it is made current again
+bool lmd_vmix_one_slot(const Dev& d);
+void launch_lmd_vmix(const Dev& d, hipStream_t s, const Tlev& t, int tind, bool one_slot = false);
 // ADV_ISONEUTRAL (k_iso.hip): prsgrd's corrector slopes (+ their exchange),
 // step3d_uv2's diff3u/diff3v/idRz over its flux-correction ranges and their
 // exchange, and step3d_t's rotated biharmonic operator for one tracer

@@ -77,6 +77,12 @@ struct Ctx {
   // host writes Akt through any entry; while it holds the tracer solvers of
   // Params::t_pair carry T and S over one matrix (akt_set).
   bool akt_same = false;
+  // Whole steps that take k_kpp_int's one-slot form (lean_akt_step) leave
+  // Akt(isalt) unformed: the slot is stale, and akt_sync copies Akt(itemp)
+  // over it before anything reads it -- a host read or registered transfer, an
+  // output sampler, a routine-level pre_step3d / step3d_t.  A host write of
+  // Akt or a routine-level lmd_vmix makes it current.
+  bool akt_stale = false;
   int t_pair_cfg = 0;   // ROMS_GPU_T_PAIR as read at init
   int t_hstg_cfg = 0;   // ROMS_GPU_T_HSTG as read at init; Params::t_hstg drops bit kTHstgHz while !vgrid_valid
   std::string err;
@@ -163,6 +169,23 @@ void akt_set(bool same) {
   g.akt_same = same;
   g.d.p.t_pair = same ? g.t_pair_cfg : 0;
 }
+// slot 2 of Akt made current before a reader: one device copy of slot 1, halos included, on the library stream
+hipError_t akt_sync() {
+  if (!g.akt_stale) return hipSuccess;
+  g.akt_stale = false;
+  const long n = g.d.b.n3w;
+  return hipMemcpyAsync(g.d.f.Akt + n, g.d.f.Akt, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, g.s);
+}
+// whole steps: lmd_vmix in its one-slot form.  Only where both tracer solvers of the step are the pair kernels
+// (launch_pre_step3d, launch_step3d_t: every lmd_vmix of a step is followed by akt_lmd_done, which puts
+// t_pair_cfg in force under the conditions below), so nothing in the step reads Akt(isalt)
+bool lean_akt_step() {
+  const Params& P = g.d.p;
+  const Bounds& b = g.d.b;
+  return (P.lean_st & kLeanAkt) && g.cfg.lmd_mixing && !P.lmd_ddmix && b.nTS == 2 && b.NT == 2 &&
+         std::memcmp(&P.Akt_bak[0], &P.Akt_bak[1], sizeof(double)) == 0 && g.t_pair_cfg == kTPairAll && P.colseg &&
+         P.seg_buf && !P.iso && lmd_vmix_one_slot(g.d);
+}
 // lmd_vmix was launched: its Akt(isalt) is its Akt(itemp) unless LMD_DDMIX or unequal backgrounds part them
 void akt_lmd_done() {
   const Params& P = g.d.p;
@@ -172,7 +195,7 @@ void akt_lmd_done() {
 // the host wrote field `id`: Hz, z_r, z_w, h, hinv or a Cs table ends VGrid's validity,
 // Akt the equality of its two slots (captured steps form both anew before they read either)
 void vg_host_write(int id) {
-  if (id == ROMS_Akt) akt_set(false);
+  if (id == ROMS_Akt) { akt_set(false); g.akt_stale = false; }
   if (id != ROMS_Hz && id != ROMS_z_r && id != ROMS_z_w && id != ROMS_h && id != ROMS_hinv && id != ROMS_Cs_w &&
       id != ROMS_Cs_r)
     return;
@@ -467,6 +490,7 @@ hipError_t roms::shim_field_h2d(int id, double* dev, const double* host) { retur
 hipError_t roms::shim_rows_h2d(double* dev, const double* host, long rows) { return rows_h2d(dev, host, rows); }
 hipError_t roms::shim_rows_d2h(double* host, const double* dev, long rows) { return rows_d2h(host, dev, rows); }
 bool roms::shim_vgrid_valid() { return g.vgrid_valid; }
+hipError_t roms::shim_akt_sync() { return akt_sync(); }
 void roms::shim_extract_huv(bool on) { g.hzuv_ext = on; }
 bool roms::shim_hzuv_valid() { return g.hzuv_valid; }
 double* roms::shim_scratch_small(long n) {
@@ -542,22 +566,33 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   // none of set_HUV's or omega's outputs, so on a multi-rank run it goes first
   // and covers set_HUV's exchange (Akv, Akt, hbls, hbbl follow on the halo stream)
   const bool lmd_early = xo && g.cfg.lmd_mixing;
-  if (lmd_early) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nstp))); akt_lmd_done(); }
+  // Akt(isalt) stays unformed through the step when its tracer solvers read one slot (lean_akt_step)
+  const bool lean_akt = lean_akt_step();
+  if (lean_akt) g.akt_stale = true;
+  if (lmd_early) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nstp, lean_akt))); akt_lmd_done(); }
   XJOIN_T(1, x_huv);   // omega reads FlxU(iend+1), FlxV(jend+1)
   // the predictor's omega also forms pre_step3d's Hz_bak/Hz_fwd (nothing in
   // between -- lmd_vmix, prsgrd -- writes FlxU, FlxV, Hz, We or Wi)
   bool hb_done = false;
   TIMED(ROMS_R_OMEGA, DEFER(hb_done = launch_omega(d, s, T, d.p.omega_hb && d.p.hoist && T.nrhs != 3 ?
                                                                  0.5 * pre_step3d_dtau(d, T) : 0.0)));
-  if (g.cfg.lmd_mixing && !lmd_early) { TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp)); akt_lmd_done(); }   // (d is g.d)
+  if (g.cfg.lmd_mixing && !lmd_early) { TIMED(ROMS_R_LMD_VMIX, launch_lmd_vmix(d, s, T, T.nstp, lean_akt)); akt_lmd_done(); }   // (d is g.d)
   // the horizontal momentum r.h.s. of pre_step3d / step3d_uv1 rides in the
   // prsgrd kernel just before them (prsgrd_can_fuse_uv; nothing between the
   // two touches u, v(nrhs), FlxU, FlxV, Hz or ru, rv); it reads neither We, Wi
   // nor the mixing coefficients, whose exchanges it covers
   const bool fuse_uv = prsgrd_can_fuse_uv(d);
+  // the predictor's u, v(indx) = Hz*u(nstp) stay unstored when step3d_uv1 below
+  // forms them again (lean_uv_step: both segment solvers in their LDS buffer
+  // forms).  Nothing in between reads u, v(indx): pre_step3d's rivers,
+  // u3dbc/v3dbc and set_HUV1 (with its exchange and rim strips) work on
+  // u, v(nnew = 3), the OBC forms read nstp and nrhs besides, omega, rho_eos,
+  // lmd_vmix and prsgrd read u, v(nrhs = 3) at most, and the output samplers
+  // run between steps; Hz changes only in the fast loop after step3d_uv1
+  const bool lean_uv = lean_uv_step(d, T);
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 0 : -1, p_ready));
   XJOIN_T(2, xt);   // pre_step3d reads We, Akv, Akt across the halo
-  TIMED(ROMS_R_PRE_STEP3D, DEFER(launch_pre_step3d(d, s, T, fuse_uv, hb_done)));   // t(nnew)
+  TIMED(ROMS_R_PRE_STEP3D, DEFER(launch_pre_step3d(d, s, T, fuse_uv, hb_done, lean_uv)));   // t(nnew)
   const long x_pre = xt;
   // set_HUV1 reads u, v(nnew), Hz and the barotropic averages, no tracer
   TIMED(ROMS_R_SET_HUV1, DEFER(launch_set_huv1(d, s, T)));   // FlxU, FlxV, u, v(nnew)
@@ -578,11 +613,11 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   }
   frc_step_phase(d, s, 2, pot);     // set_forces, '1/2 fwd' (main.F:433)
   launch_bulk_flux(d, s, T.nrhs);   // set_forces (main.F:433): BULK_FRC only
-  if (g.cfg.lmd_mixing) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs))); akt_lmd_done(); }   // Akv, Akt, hbls, hbbl
+  if (g.cfg.lmd_mixing) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs, lean_akt))); akt_lmd_done(); }   // Akv, Akt, hbls, hbbl
   frc_step_phase(d, s, 3, pot);     // set_bry_all 'forward' + set_tides (main.F:438-441)
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 1 : -1, p_ready));
   XJOIN_T(16, xt);   // step3d_uv1 reads We and Akv across the halo
-  TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_uv));
+  TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_uv, lean_uv));
   if (g.cfg.uv_vis2) TIMED(ROMS_R_VISC3D, launch_visc3d(d, s, T));
   // the fast loop is timed as one interval over its nfast steps (kernel-level
   // count, as the graph replays it: no event between two fast steps)
@@ -932,6 +967,10 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   P.t_pair = 0;
   g.akt_same = false;
   (void)t_pair_launches(0, 0, true);
+  // stores of a whole step that nothing in the step reads (bits in
+  // roms_dev.h); ROMS_GPU_LEAN_ST=0 for every store
+  P.lean_st = env_int("ROMS_GPU_LEAN_ST", kLeanDefault, 0, kLeanAll);
+  (void)lean_st_launches(0, 0, true);
   // the horizontal tracer kernels as one block per tile walking the levels
   // over staged windows (bits in roms_dev.h; bit 4, Hz formed in the
   // predictor, in force under the grid's validity flag and with bit 1 only);
@@ -1148,6 +1187,7 @@ static int xfer(int id, bool up) {
   if (!up && !hzuv_readable(id)) return -5;
   if (up && (id == ROMS_Hz_u || id == ROMS_Hz_v)) g.hzuv_valid = true;
   if (up) vg_host_write(id);
+  else if (id == ROMS_Akt) CHECK_HIP(akt_sync());
   CHECK_HIP(up ? field_h2d(id, g.f[id].d, g.f[id].host) : field_d2h(id, g.f[id].host, g.f[id].d));
   return 0;
 }
@@ -1166,6 +1206,7 @@ int roms_gpu_copy_out(int id, double* dst, long count) {
   REQUIRE_INIT_RO();
   if (id < 0 || id >= ROMS_NFIELDS || count != g.f[id].hcount) { g.err = "roms_gpu_copy_out: bad field/size"; return -1; }
   if (!hzuv_readable(id)) return -5;
+  if (id == ROMS_Akt) CHECK_HIP(akt_sync());
   CHECK_HIP(field_d2h(id, dst, g.f[id].d));
   REQUIRE_HALO_OK();
   return 0;
@@ -1187,12 +1228,12 @@ int roms_gpu_sync(void) {
 ROUTINE(roms_gpu_set_huv, (launch_set_huv(g.d, g.s, T), g.hzuv_valid = true))
 ROUTINE(roms_gpu_omega, launch_omega(g.d, g.s, T))
 ROUTINE(roms_gpu_prsgrd, launch_prsgrd(g.d, g.s, T))
-ROUTINE(roms_gpu_pre_step3d, launch_pre_step3d(g.d, g.s, T))
+ROUTINE(roms_gpu_pre_step3d, ((void)akt_sync(), launch_pre_step3d(g.d, g.s, T)))
 ROUTINE(roms_gpu_set_huv1, launch_set_huv1(g.d, g.s, T))
 ROUTINE(roms_gpu_step3d_uv1, launch_step3d_uv1(g.d, g.s, T))
 ROUTINE(roms_gpu_visc3d, launch_visc3d(g.d, g.s, T))
 ROUTINE(roms_gpu_step3d_uv2, launch_step3d_uv2(g.d, g.s, T))
-ROUTINE(roms_gpu_step3d_t, launch_step3d_t(g.d, g.s, T))
+ROUTINE(roms_gpu_step3d_t, ((void)akt_sync(), launch_step3d_t(g.d, g.s, T)))
 ROUTINE(roms_gpu_t3dmix, launch_t3dmix(g.d, g.s, T))
 ROUTINE(roms_gpu_set_depth, (launch_set_depth(g.d, g.s, T), vg_set(true)))
 #undef ROUTINE
@@ -1231,6 +1272,12 @@ int roms_gpu_tracer_pair(long launches[2]) {
   REQUIRE_INIT_NOJOIN();
   if (launches) { launches[0] = t_pair_launches(kTPairPre); launches[1] = t_pair_launches(kTPairCor); }
   return g.t_pair_cfg + (g.akt_same ? 256 : 0);
+}
+
+int roms_gpu_lean_stores(long launches[2]) {
+  REQUIRE_INIT_NOJOIN();
+  if (launches) { launches[0] = lean_st_launches(kLeanUv); launches[1] = lean_st_launches(kLeanAkt); }
+  return g.d.p.lean_st;
 }
 
 int roms_gpu_tracer_hstg(long launches[3]) {
@@ -1309,7 +1356,8 @@ int roms_gpu_lmd_vmix(int tind, const roms_tlev* t) {
   REQUIRE_INIT();
   if (!g.cfg.lmd_mixing) { g.err = "roms_gpu_lmd_vmix: library initialised without lmd_mixing"; return -4; }
   if (tind < 1 || tind > 3) { g.err = "roms_gpu_lmd_vmix: bad time index"; return -1; }
-  launch_lmd_vmix(g.d, g.s, to_tlev(t), tind);
+  launch_lmd_vmix(g.d, g.s, to_tlev(t), tind);   // the routine stores both slots
+  g.akt_stale = false;
   akt_lmd_done();
   return post_launch();
 }
@@ -1504,7 +1552,8 @@ int roms_gpu_step(roms_tlev* t) {
   // the grid's validity at entry decides the forms ahead of the step's own
   // set_depth; the step leaves it valid either way
   const long key = (long)t->nstp * 16 + t->knew + (rho_current ? 256 : 0) + (store_huv ? 512 : 0) +
-                   (g.vgrid_valid ? 1024 : 0);
+                   (g.vgrid_valid ? 1024 : 0) + (lean_uv_step(g.d, to_tlev(t)) ? 2048 : 0) +
+                   (lean_akt_step() ? 4096 : 0);
   auto it = g.graphs.find(key);
   roms_tlev t0 = *t;
   if (it == g.graphs.end()) {
@@ -1523,6 +1572,7 @@ int roms_gpu_step(roms_tlev* t) {
   CHECK_HIP(hipGraphLaunch(it->second, g.s));
   vg_set(true);   // the replayed step ran set_depth
   if (g.cfg.lmd_mixing) akt_lmd_done();   // and lmd_vmix
+  if (lean_akt_step()) g.akt_stale = true;   // in its one-slot form
   t->nrhs = 3;
   t->nnew = 3 - t->nstp;
   g.rho_slot = t->nnew;   // the replayed step ended with rho_eos(nnew)

@@ -256,6 +256,7 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   if (!rst && (mask & ROMS_WRT_AKV)) add("AKv", "vertical viscosity coefficient", "meter2 second-1", 'r', N + 1, av ? av->akv : F.Akv, n2);
   if (!rst && (mask & ROMS_WRT_AKT))
     add("AKt", "temperature vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, av ? av->akt : F.Akt, n2);
+  if (!rst && (mask & ROMS_WRT_AKS) && S.cfg->salinity && !av) (void)shim_akt_sync();   // whole steps may leave Akt(isalt) unformed
   if (!rst && (mask & ROMS_WRT_AKS) && S.cfg->salinity)
     add("AKs", "salinity vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, av ? av->aks : F.Akt + b.n3w, n2);
   const bool kpp = S.cfg->lmd_mixing != 0;

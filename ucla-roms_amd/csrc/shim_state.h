@@ -85,6 +85,9 @@ struct ZslView {
 // when do_avg), through the snapshot and writer thread of the other records
 int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv);
 void zslice_free();            // roms_gpu_finalize
+// Akt(isalt) made current on the library stream before a kernel or copy reads it (whole steps may leave it
+// unformed while it is Akt(itemp) bit for bit: roms_shim.cpp akt_stale)
+hipError_t shim_akt_sync();
 bool shim_vgrid_valid();       // the stored Hz, z_r, z_w are set_depth's own (VGrid may stand in for them)
 // Child-boundary extraction (k_extract.hip): one record of an extraction file
 // for rst_io.hip's writer thread.  Every variable lies packed, (levels, np)

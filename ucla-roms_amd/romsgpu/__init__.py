@@ -643,6 +643,16 @@ class Model:
         self._chk(min(r, 0), "tracer_pair")
         return r % 256, bool(r // 256), (n[0], n[1])
 
+    def lean_stores(self):
+        """(mask, (uv, akt)): the stores whole steps leave out
+        (ROMS_GPU_LEAN_ST, as read at init: 1 the predictor's u, v(indx),
+        2 lmd_vmix's Akt(isalt)) and the pre_step3d and lmd_vmix launches
+        enqueued since init that left theirs out (roms_gpu_lean_stores)."""
+        n = (ctypes.c_long * 2)(0, 0)
+        r = self.L.roms_gpu_lean_stores(n)
+        self._chk(min(r, 0), "lean_stores")
+        return r, (n[0], n[1])
+
     def tracer_hstg(self):
         """(mask, valid, (pre, cor, pre_hz)): the horizontal tracer kernels
         that walk the levels over staged windows (ROMS_GPU_T_HSTG, as read at
