@@ -124,16 +124,19 @@ def routine_list(cfg):
 _ROUTINE_CASE = {}   # one entry: the configuration last asked for
 
 
-def routine_case(cfg):
+def routine_case(cfg, setup=None, tag=b""):
     """The oracle of configuration cfg after 3 steps with perturbed mixing and
     implicit fluxes, a copy of its whole state, and the per-routine reference
     outputs (filled on first use, shared by every model of the same
-    configuration that follows: the default and the forced one)."""
-    key = bytes(cfg)
+    configuration that follows: the default and the forced one).  setup(o)
+    runs between init and the steps; tag tells its states from the plain one."""
+    key = bytes(cfg) + tag
     if key in _ROUTINE_CASE:
         return _ROUTINE_CASE[key]
     o = oracle.Oracle(cfg)
     o.init()
+    if setup is not None:
+        setup(o)
     o.step(3)
     rng = np.random.default_rng(11)
     for name in ("Akv", "Akt"):
@@ -147,12 +150,12 @@ def routine_case(cfg):
     return _ROUTINE_CASE[key]
 
 
-def routine_errors(cfg, m, only=None):
+def routine_errors(cfg, m, only=None, setup=None, tag=b""):
     """Every routine on the same state of configuration cfg, oracle and GPU:
     {(id, field): error} relative to the field's interior maximum (Wi: to
     We's, as in test_gpu_colseg.test_omega_blocks -- where the Courant split
     leaves Wi zero it is cancellation noise)."""
-    cfg, o, snap, tix, refs = routine_case(cfg)
+    cfg, o, snap, tix, refs = routine_case(cfg, setup, tag)
     iic, kstp, knew, nstp = tix[:4]
     errs = {}
     for rid, routine, mode, outs in routine_list(cfg):

@@ -48,10 +48,11 @@ def _case(kind):
                 sizex=72e3, sizey=56e3, lmd=(kind == "basin_lmd"))
 
 
-def run_decomposed(case, npx, npe, nsteps, fields=FIELDS, diag=False, probe=None):
+def run_decomposed(case, npx, npe, nsteps, fields=FIELDS, diag=False, probe=None, setup=None):
     """Run every subdomain in its own thread; returns per-rank field dicts
     (and per-step diag norms of rank 0 when diag=True); probe(model) after
-    the steps lands as the 6th item of each rank's tuple."""
+    the steps lands as the 6th item of each rank's tuple; setup(model) runs
+    on every rank right after its model is made."""
     n = npx * npe
     _group[0] += 1
     grp = _group[0]
@@ -61,6 +62,8 @@ def run_decomposed(case, npx, npe, nsteps, fields=FIELDS, diag=False, probe=None
         try:
             h = romsgpu.comm_create_local(grp, n, rank)
             m = romsgpu.Model.from_case(np_xi=npx, np_eta=npe, comm=h, rank=rank, **case)
+            if setup is not None:
+                setup(m)
             if diag:   # diag is collective: every rank calls it
                 d = m.diag()
                 if rank == 0:
@@ -95,18 +98,21 @@ EXCHANGED = ("zeta", "ubar", "vbar", "u", "v", "t", "FlxU", "FlxV", "We", "Wi", 
 LMD_FIELDS = ("Akv", "Akt", "hbls", "hbbl", "ghat", "swr_frac")
 
 
-def check_decomposition(case, npx, npe, nsteps=5, fields=None, probe=None):
+def check_decomposition(case, npx, npe, nsteps=5, fields=None, probe=None, setup=None):
     """Every subdomain of an npx x npe run equals the single-domain run's
     window bitwise (owned cells, and halos of the exchanged fields);
-    probe(model) runs on every rank after the steps (run_decomposed)."""
+    probe(model) runs on every rank after the steps, setup(model) on the
+    single domain and on every rank before them (run_decomposed)."""
     per = case["case_id"] == 0
     if fields is None:
         fields = FIELDS + (LMD_FIELDS if case.get("lmd") else ())
     m = romsgpu.Model.from_case(**case)
+    if setup is not None:
+        setup(m)
     m.step(nsteps)
     ref = {f: m.get(f) for f in fields}
     m.close()
-    parts, _ = run_decomposed(case, npx, npe, nsteps, fields=fields, probe=probe)
+    parts, _ = run_decomposed(case, npx, npe, nsteps, fields=fields, probe=probe, setup=setup)
     bad = []
     for rank, (iSW, jSW, Lm, Mm, got, _) in enumerate(parts):
         jn, inn = divmod(rank, npx)
