@@ -285,7 +285,7 @@ int roms_gpu_halo_transport(void);
  * fast step, as step2d_FB.F:572-574; multi-rank runs without open edges
  * default to 4, ROMS_GPU_S2D_K=1..8; K is lowered until 2K+2 fits the
  * smallest subdomain of the mpi_setup.F split, the same on every rank;
- * rivers and pipes take every step).                                         */
+ * with rivers or pipes on every fast step exchanges, and 1 is reported).      */
 int roms_gpu_halo_exchanges(long *per_step, int *fast_interval);
 /* 1 if whole steps defer each producer's 3-D exchange onto the halo stream
  * beside the next routine that reads none of its halo (the default with

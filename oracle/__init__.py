@@ -95,6 +95,8 @@ def lib():
         L.or_set_iif.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.or_set_river.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_double)]
+        L.or_set_river_faces.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.POINTER(ctypes.c_double)] * 4
+        L.or_set_river_faces.restype = ctypes.c_int
         L.or_set_ub.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_double)] * 4
         L.or_frc_record.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_double,
                                     ctypes.POINTER(ctypes.c_double)]
@@ -205,12 +207,37 @@ class Oracle:
         w = np.ctypeslib.as_array(p, shape=(2 * 288,)).reshape(2, 288)
         return w.copy()
 
+    def _river_args(self, vol, trc):
+        """riv_vol (nriv,) and riv_trc (nriv, NT) as the oracle stores them
+        (column-major); a scalar vol with trc (NT,) is one river."""
+        v = np.ascontiguousarray(vol, dtype=np.float64).reshape(-1)
+        nriv = v.size
+        t = np.asarray(trc, dtype=np.float64).reshape(nriv, -1)
+        if not 1 <= nriv <= 16 or t.shape[1] != self.cfg.NT:
+            raise ValueError("rivers: nriv = %d (1..16), riv_trc %s for NT = %d" % (nriv, t.shape, self.cfg.NT))
+        return nriv, v, np.asfortranarray(t).ravel(order="F")
+
     def set_river(self, vol, trc):
-        """river_frc.F set_river_frc for one river: riv_vol, riv_trc(1:NT)."""
-        v = np.ascontiguousarray([vol], dtype=np.float64)
-        t = np.ascontiguousarray(trc, dtype=np.float64)
+        """river_frc.F set_river_frc: riv_vol (nriv,), riv_trc (nriv, NT), the
+        faces kept; one river as set_river(vol, (T, S))."""
+        nriv, v, t = self._river_args(vol, trc)
         P = ctypes.POINTER(ctypes.c_double)
-        self.L.or_set_river(self.h, 1, v.ctypes.data_as(P), t.ctypes.data_as(P))
+        self.L.or_set_river(self.h, nriv, v.ctypes.data_as(P), t.ctypes.data_as(P))
+
+    def set_river_faces(self, vol, trc, uflx, vflx):
+        """calc_river_flux's riv_uflx / riv_vflx on the (Mm+4, Lm+4) layout
+        with riv_vol (nriv,) and riv_trc (nriv, NT); switches river_source on
+        in any case.  ValueError on a face whose river index is outside
+        1..nriv."""
+        nriv, v, t = self._river_args(vol, trc)
+        uf = np.ascontiguousarray(uflx, dtype=np.float64).ravel()
+        vf = np.ascontiguousarray(vflx, dtype=np.float64).ravel()
+        if uf.size != self.nx2 * self.ny2 or vf.size != uf.size:
+            raise ValueError("set_river_faces: planes of %d and %d elements" % (uf.size, vf.size))
+        P = ctypes.POINTER(ctypes.c_double)
+        if self.L.or_set_river_faces(self.h, nriv, uf.ctypes.data_as(P), vf.ctypes.data_as(P), v.ctypes.data_as(P),
+                                     t.ctypes.data_as(P)) != 0:
+            raise ValueError("or_set_river_faces: a face's river index is outside 1..%d" % nriv)
 
     def set_ub(self, ub):
         """SPONGE_TUNE ub_west/east/south/north (sequence of 4 arrays or None)."""

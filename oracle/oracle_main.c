@@ -974,3 +974,25 @@ void or_set_river(or_state *S, int nriv, const double *vol, const double *trc) {
   for (int r = 0; r < nriv; r++) S->riv_vol[r] = vol[r];
   for (int q = 0; q < nriv * S->NT; q++) S->riv_trc[q] = trc[q];
 }
+
+/* River faces as calc_river_flux (river_frc.F:242-279) leaves them, given by
+ * the caller: whole (-1:Lm+2, -1:Mm+2) planes of 10*iriver + signed fraction,
+ * with riv_vol(nriv) and riv_trc(nriv,NT) column-major.  Switches
+ * river_source on in any case.  Nonzero, with nothing changed, on a bad
+ * count or a face (|riv_flx| > 1e-3, step2d_FB.F:534) whose nint(riv_flx/10)
+ * is outside 1..nriv. */
+int or_set_river_faces(or_state *S, int nriv, const double *uflx, const double *vflx, const double *vol,
+                       const double *trc) {
+  if (nriv < 1 || nriv > 16 || nriv * S->NT > 256 || !uflx || !vflx || !vol || !trc) return 1;
+  for (size_t q = 0; q < S->n2; q++)
+    for (int dir = 0; dir < 2; dir++) {
+      const double v = dir == 0 ? uflx[q] : vflx[q];
+      if (!(fabs(v) > 1e-3)) continue;
+      const long ir = lround(v / 10);
+      if (ir < 1 || ir > nriv) return 2;
+    }
+  for (size_t q = 0; q < S->n2; q++) { S->riv_uflx[q] = uflx[q]; S->riv_vflx[q] = vflx[q]; }
+  S->river_source = 1;
+  or_set_river(S, nriv, vol, trc);
+  return 0;
+}

@@ -105,6 +105,11 @@ void or_set_iif(or_state *S, int iif);
 void or_scalars(const or_state *S, double out[5]);
 /* set_river_frc: new riv_vol(nriv), riv_trc(nriv,NT) (faces kept) */
 void or_set_river(or_state *S, int nriv, const double *vol, const double *trc);
+/* calc_river_flux's result from the caller: riv_uflx, riv_vflx as whole
+   (Mm+4) x (Lm+4) planes (10*iriver + signed fraction), nriv = 1..16 rivers;
+   sets river_source on any case; nonzero on a face index outside 1..nriv */
+int or_set_river_faces(or_state *S, int nriv, const double *uflx, const double *vflx, const double *vol,
+                       const double *trc);
 void or_set_ub(or_state *S, const double *w, const double *e, const double *s, const double *n);
 
 #ifdef __cplusplus

@@ -109,7 +109,8 @@ def test_river_count_below_face_indices_is_rejected():
     """Faces kept from an earlier call index riv_vol up to their largest river
     number: a smaller nriv without new faces fails loudly instead of reading
     past the new arrays on the device; with the faces passed
-    again it is accepted."""
+    again it is accepted, and two rivers through two u faces then run as the
+    oracle's given the same faces (3 steps of the closed basin, RMS_RUN)."""
     m = romsgpu.Model.from_case(3, 40, 40, 10, 2, salinity=True, nonlin_eos=True, dt=20.0, ndtfast=30,
                                 sizex=10e3, sizey=10e3, lmd=True)
     uf = np.zeros((42 + 2, 42 + 2))
@@ -122,4 +123,19 @@ def test_river_count_below_face_indices_is_rejected():
     uf[11, 5] = 0.0
     m.set_river_frc([500.0], [[24.0, 1.0]], uf, vf)   # new faces: accepted
     m.step(1)
+    m.close()
+    # what the accepted faces do is the oracle's: the same two u faces, two rivers, in the closed basin
+    from test_gpu_parity import basin_cfg, make_pair as basin_pair
+    cfg = basin_cfg(nonlin=True)
+    o, m = basin_pair(cfg)
+    uf = np.zeros((cfg.MMm + 4, cfg.LLm + 4))
+    vf = np.zeros_like(uf)
+    uf[10, 5], uf[11, 5] = 10 * 1 + 0.5, 10 * 2 + 0.5
+    vol, trc = [5.0e4, 3.0e4], [[24.0, 1.0], [20.0, 2.0]]
+    o.set_river_faces(vol, trc, uf, vf)
+    m.set_river_frc(vol, trc, uf, vf)
+    o.step(3)
+    m.step(3)
+    assert float(np.abs(o.field("u")[:, 10:12, 5]).max()) > 1e-4     # the faces flow
+    check_fields(o, m, PROGNOSTIC, cfg.LLm, cfg.MMm, RMS_RUN, kind="rms")
     m.close()

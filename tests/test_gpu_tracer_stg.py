@@ -56,6 +56,9 @@ DEPTHS = [5, 88]
 
 
 def _cfg(case, LLm, MMm, N):
+    if not isinstance(case, str):   # a configuration of the caller's (tests/test_gpu_rivers_sweep.py)
+        assert (case.LLm, case.MMm, case.N) == (LLm, MMm, N)
+        return case
     if case == "filament":   # doubly periodic, T and S
         return oracle.filament_cfg(LLm=LLm, MMm=MMm, N=N, NT=2, salinity=True, sizex=200.0 * LLm, sizey=50.0 * MMm,
                                    np_xi=1, np_eta=1)
@@ -100,15 +103,19 @@ def oracle_state():
     """Per (case, LLm, MMm, N, routine): the oracle after 4 steps with the
     routine's indices set (the predictor's for pre_step3d, the corrector's
     for step3d_t), its fields before the routine and t after set_depth + the
-    routine (formed once, left unchanged)."""
+    routine (formed once, left unchanged).  setup = (tag, on_oracle,
+    on_model): on_oracle(o) runs between init and the steps, tag tells its
+    states from the plain ones."""
     cache = {}
 
-    def get(case, LLm, MMm, N, routine):
-        key = (case, LLm, MMm, N, routine)
+    def get(case, LLm, MMm, N, routine, setup=None):
+        key = (case if isinstance(case, str) else bytes(case), LLm, MMm, N, routine, setup[0] if setup else None)
         if key not in cache:
             cfg = _cfg(case, LLm, MMm, N)
             o = oracle.Oracle(cfg)
             o.init()
+            if setup is not None:
+                setup[1](o)
             o.step(4)
             iic, kstp, knew, nstp, nrhs, nnew = o.tindex()
             tix = [iic, kstp, knew, nstp, nstp, 3] if routine == "pre_step3d" else [iic, kstp, knew, nstp, 3, 3 - nstp]
@@ -132,12 +139,17 @@ def _prepare(m, tix, nfast, before):
     assert m.tracer_hstg()[1] is True
 
 
-def _routine_under_every_mask(case, LLm, MMm, N, routine, oracle_state, monkeypatch):
-    cfg, tix, nfast, before, t_after = oracle_state(case, LLm, MMm, N, routine)
+def _routine_under_every_mask(case, LLm, MMm, N, routine, oracle_state, monkeypatch, setup=None):
+    """setup = (tag, on_oracle, on_model) as oracle_state takes it; on_model(m)
+    runs on every model before the oracle's state goes in.  Returns the
+    fields of the per-level kernels' model (mask 0) after the routine."""
+    cfg, tix, nfast, before, t_after = oracle_state(case, LLm, MMm, N, routine, setup)
     assert cfg.NT == 2
     outs = []
     for mask in MASKS:
         m = _model(cfg, monkeypatch, mask)
+        if setup is not None:
+            setup[2](m)
         _prepare(m, tix, nfast, before)
         assert m.tracer_hstg()[2] == (0, 0, 0)
         getattr(m, routine)()
@@ -153,6 +165,7 @@ def _routine_under_every_mask(case, LLm, MMm, N, routine, oracle_state, monkeypa
     for mask, out in zip(MASKS[1:], outs[1:]):
         _assert_same(outs[0], out, mask)
     assert not np.array_equal(outs[0]["t"], before["t"])
+    return outs[0]
 
 
 # ---- 1.-3. routine parity on the grids and depths, closed basin ----

@@ -924,6 +924,16 @@ __global__ void k_s2d_edges(Dev d, FBCoef c, int phase) {
 
 void launch_fast_step(const Dev& d, hipStream_t s, const FBCoef& c, const Tlev& t);
 
+// The fast loop's exchange interval this rank takes now (launch_step2d,
+// roms_gpu_halo_exchanges): Params::s2d_k on a multi-rank run with the wide
+// halos for it, 1 with rivers or pipes (their face lists are the owner's)
+// and with the split kernels.
+int s2d_exchange_interval(const Dev& d) {
+  const Halo* Hk = d.halo;
+  return (d.p.s2d_k > 1 && Hk && Hk->comm && Hk->wide.g.w == 2 * d.p.s2d_k && d.p.npip == 0 && d.p.nriv == 0 &&
+          !d.p.s2d_split) ? d.p.s2d_k : 1;
+}
+
 void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1, const double* w2) {
   const Bounds& b = d.b;
   FBCoef c;
@@ -957,8 +967,7 @@ void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1,
   // first fast step.  Rivers and pipes (their face lists are the owner's)
   // take every step.
   const Halo* Hk = d.halo;
-  const int K = (d.p.s2d_k > 1 && Hk && Hk->comm && Hk->wide.g.w == 2 * d.p.s2d_k && d.p.npip == 0 &&
-                 d.p.nriv == 0 && !d.p.s2d_split) ? d.p.s2d_k : 1;
+  const int K = s2d_exchange_interval(d);
   const int gend = K > 1 ? ((t.iif - 1) / K + 1) * K < t.nfast ? ((t.iif - 1) / K + 1) * K : t.nfast : t.iif;
   Dev de = d;   // the bounds this fast step updates
   if (K > 1) {
@@ -984,6 +993,13 @@ void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1,
     e.jendR = e.north_edge ? e.jend + 1 : e.jend;
   }
   launch_fast_step(de, s, c, t);
+  // A river face in a rank's first owned column or row divides by Dnew of the
+  // cell beyond it (step2d_FB.F:538, 549; the reference forms Dnew one cell
+  // beyond its own points), which here is zeta(knew) of the neighbour's cell:
+  // on a decomposed grid that level crosses before the hook, ubar and vbar
+  // with the faces set after it.  d.p.nriv is the same on every rank.
+  const bool riv_halo = d.p.nriv > 0 && Hk && Hk->comm && !d.p.s2d_split;
+  if (riv_halo) launch_exchange_list(d, s, ExchList{{d.f.zeta + (long)(t.knew - 1) * b.n2}, {1}, 1});
   launch_river_s2d(d, s, t.knew);   // step2d_FB.F:531-554
   const int vwrap = (d.halo == nullptr && !d.p.s2d_split) ? (b.ew_periodic ? 1 : 0) | (b.ns_periodic ? 2 : 0) : 0;
   if (t.iif == t.nfast)   // zeta(knew) = Zt_avg1 (step2d_FB.F:566) inside set_depth's kernel, same range
@@ -1013,7 +1029,9 @@ void launch_step2d(const Dev& d, hipStream_t s, const Tlev& t, const double* w1,
     return;
   }
   const long kn = (long)(t.knew - 1) * b.n2;
-  const ExchList L{{d.f.zeta + kn, d.f.ubar + kn, d.f.vbar + kn}, {1, 1, 1}, 3};
+  // (the last fast step's set_depth has put Zt_avg1 into zeta(knew) since: that one crosses again)
+  const ExchList L = riv_halo && t.iif < t.nfast ? ExchList{{d.f.ubar + kn, d.f.vbar + kn}, {1, 1}, 2}
+                                                 : ExchList{{d.f.zeta + kn, d.f.ubar + kn, d.f.vbar + kn}, {1, 1, 1}, 3};
   Halo* H = const_cast<Halo*>(d.halo);
   if (H && H->overlap && t.iif < t.nfast && !d.p.s2d_split) {
     // overlap the exchange with the next fast step's interior tiles; that

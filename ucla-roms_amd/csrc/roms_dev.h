@@ -560,6 +560,7 @@ void launch_t3dmix(const Dev& d, hipStream_t s, const Tlev& t);
 void launch_u3dbc(const Dev& d, hipStream_t s, const Tlev& t);
 // river_frc.F hooks (k_river.hip): ubar/vbar(knew) and DU/DV_avg1 at river
 // faces after each fast step; u,v(nnew) at river faces (pred: predictor ranges)
+int s2d_exchange_interval(const Dev& d);   // the fast loop's exchange interval in force (k_step2d.hip)
 void launch_river_s2d(const Dev& d, hipStream_t s, int knew);
 // BULK_FRC: calc_all_bulk_forces (k_bulk.hip)
 void launch_bulk_flux(const Dev& d, hipStream_t s, int nrhs);

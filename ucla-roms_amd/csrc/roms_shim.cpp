@@ -1334,7 +1334,7 @@ int roms_gpu_horizontal_path(int out[8]) {
 int roms_gpu_halo_exchanges(long* per_step, int* fast_interval) {
   REQUIRE_INIT_NOJOIN();
   if (per_step) *per_step = g.step_exch;
-  if (fast_interval) *fast_interval = g.d.p.s2d_k;
+  if (fast_interval) *fast_interval = s2d_exchange_interval(g.d);   // 1 while rivers or pipes are on
   return 0;
 }
 

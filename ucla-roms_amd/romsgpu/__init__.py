@@ -481,17 +481,15 @@ class Model:
     def set_river_frc(self, riv_vol, riv_trc, riv_uflx=None, riv_vflx=None):
         """river_frc.F:set_river_frc: riv_vol (nriv,), riv_trc (nriv, NT) for the
         current time; riv_uflx/riv_vflx on the (Mm+4, Lm+4) grid as
-        calc_river_flux leaves them (None: keep the faces already set)."""
+        calc_river_flux leaves them (None: keep the faces already set).  No
+        river (riv_vol empty) switches river_source off."""
         vol = np.ascontiguousarray(riv_vol, dtype=np.float64).ravel()
         nriv = vol.shape[0]
-        trc = np.asfortranarray(np.asarray(riv_trc, dtype=np.float64).reshape(nriv, -1)).ravel(order="F")
+        trc = np.asarray(riv_trc, dtype=np.float64)
+        trc = np.asfortranarray(trc.reshape(nriv, -1)).ravel(order="F") if nriv else trc.ravel()
         P = ctypes.POINTER
         D = P(ctypes.c_double)
-        if riv_uflx is None:
-            uf = vf = None
-        else:
-            uf = np.ascontiguousarray(riv_uflx, dtype=np.float64).ravel()
-            vf = np.ascontiguousarray(riv_vflx, dtype=np.float64).ravel()
+        uf, vf = (None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (riv_uflx, riv_vflx))
         self._chk(self.L.roms_gpu_set_river_frc(nriv, uf.ctypes.data_as(D) if uf is not None else None,
                                                 vf.ctypes.data_as(D) if vf is not None else None,
                                                 vol.ctypes.data_as(D), trc.ctypes.data_as(D)), "set_river_frc")
