@@ -3,8 +3,8 @@
 ctypes binding of oracle/_ref/libref_<name>.so, which build_ref.sh
 compiles from the reference tree, unchanged, around stand-in modules and the
 C entry points of harness.F90.  Grid size and open sides are compile-time in
-the reference, so there is one library per set of open sides (obc15, obc5,
-obc10) and one for the bulk fluxes under LMD_KPP (bulk), all at one small
+the reference, so there is one library per set of open sides (obc1 .. obc15,
+every non-empty set of the bits 1 W, 2 E, 4 S, 8 N) and one for the bulk fluxes under LMD_KPP (bulk), all at one small
 non-square grid.  tests/test_ref_pin_obc.py and
 tests/test_ref_pin_bulk.py hold the CPU oracle against these libraries on
 identical states; tests/test_gpu_bulk.py holds the HIP kernel against them.
@@ -21,7 +21,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _OUT = os.path.join(os.path.dirname(_HERE), "_ref")
 REF_TREE = os.environ.get("REF", "/root/reference")
-VARIANTS = (15, 5, 10)          # open sides of the libraries obc15, obc5, obc10
+VARIANTS = tuple(range(1, 16))  # open sides of the libraries obc1 .. obc15: every non-empty set (bits 1 W, 2 E, 4 S, 8 N)
 BULK = "bulk"                   # the library with LMD_KPP, for set_bulk_frc
 SIDES = ("west", "east", "south", "north")
 _P = ctypes.POINTER(ctypes.c_double)

@@ -14,8 +14,8 @@
 # stand-in modules (standins.F, standins_io.F), the C entry points
 # (harness.F90), the MPI shim of fortran/refbuild and the three option files
 # written below from the lists SWITCHES and SIZES.  Grid size and open sides
-# are compile-time in the reference, hence one library per set of open sides,
-# and one more for the bulk fluxes with LMD_KPP, the switch bulk_frc itself
+# are compile-time in the reference, hence one library per set of open sides
+# (all fifteen, obc1 .. obc15), and one more for the bulk fluxes with LMD_KPP, the switch bulk_frc itself
 # asks about (the short-wave flux under ice).
 #
 # Nothing is written outside oracle/_ref/, which git ignores.  Without a
@@ -39,7 +39,7 @@ SWITCHES="SOLVE3D MASKING CURVGRID OBC_M2FLATHER OBC_M3ORLANSKI OBC_TORLANSKI
 # non-square on purpose: a swapped extent shows
 SIZES="LLm=24 MMm=20 N=6 NP_XI=1 NP_ETA=1 NSUB_X=1 NSUB_E=1 nt=2"
 # library : open sides (bits 1 W, 2 E, 4 S, 8 N) : further switches
-VARIANTS="obc15:15: obc5:5: obc10:10: bulk:15:LMD_MIXING,LMD_KPP"
+VARIANTS="$(for b in 1 2 3 4 5 6 7 8 9 10 11 12 13 14 15; do printf 'obc%d:%d: ' $b $b; done)bulk:15:LMD_MIXING,LMD_KPP"
 BULK_FIELDS="uwnd vwnd tair Q prate lwrad swrad"
 
 REFSRC="param hidden_mpi_vars dimensions scalars ocean_vars private_scratch"

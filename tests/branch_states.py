@@ -21,6 +21,14 @@ tests/test_gpu_branches.py runs the HIP kernels on the same states.
                  (whole runs at that ndtfast blow up), on 2.3 km curvilinear
                  cells so that every edge has points on both sides
   cext_state     boundary data of both signs on every side of u3dbc / v3dbc
+  twin_state     a perturbed twin of flather_state for any set of open sides
+                 and any small size: noise on every time level, land on one
+                 cell of every edge, boundary velocities of both signs; with
+                 it the restatements of every data-dependent arm of the
+                 boundary routines (normal_arms, tangential_arms, tracer_arms,
+                 mask_arms, ub_arms) that tests/test_ref_pin_obc.py (against
+                 the reference) and tests/test_gpu_open_sides.py (the HIP
+                 kernels) assert before they compare
   kpp_eos_state  KPP over the linear EOS, and over the split EOS without
                  salinity
   kpp_top_state  surface heating and weak wind: the boundary layer ends
@@ -32,6 +40,8 @@ tests/test_gpu_branches.py runs the HIP kernels on the same states.
                  and unstable air, calm, every Charnock range, no rain, a
                  coast, water at and below the -1.8 degC of SEA_ICE_NOFLUX
 """
+import functools
+
 import numpy as np
 
 import oracle
@@ -186,10 +196,10 @@ def flather_cx(o, cfg):
 CEXT_FIELDS = {"west": "u_west", "east": "u_east", "south": "v_south", "north": "v_north"}
 
 
-def cext_state(mode):
+def cext_state(mode, obc=15):
     """The open basin after three steps with a sign-changing wave added to the
     normal-velocity boundary data of every side (amplitude twice the data's)."""
-    cfg = obc_cfg(obc=15)
+    cfg = obc_cfg(obc=obc)
     o = _started(cfg)
     for q, name in enumerate(CEXT_FIELDS.values()):
         a = o.field(name).reshape(cfg.N, -1)
@@ -221,6 +231,168 @@ def cext_arms(o, cfg, tix):
         out[side] = {"data in": data_in.mean(), "data out": (~data_in).mean(),
                      "ran bry arm": (inflow & data_in).mean(), "ran ubind arm": (inflow & ~data_in).mean()}
     return out
+
+
+# ------------------------------------------------------------------ twin ----
+SIDES = ("west", "east", "south", "north")
+OPEN = {"west": 1, "east": 2, "south": 4, "north": 8}
+TWIN_SIZE = dict(LLm=24, MMm=20, N=6)        # the grid of the reference libraries (oracle/ref/build_ref.sh)
+TWIN_STATE = ("zeta", "ubar", "vbar", "u", "v", "t")
+TWIN_MASKS = ("rmask", "umask", "vmask", "pmask")
+TWIN_BRY = ["%s_%s" % (v, e) for v in TWIN_STATE for e in SIDES]
+EPS = 1.0e-33
+
+
+def twin_land(LLm, MMm):
+    """One land cell on every edge, with its ghost neighbour: (i, j) in Fortran indices."""
+    return {"west": [(0, 7), (1, 7)], "east": [(LLm, 11), (LLm + 1, 11)], "south": [(9, 0), (9, 1)],
+            "north": [(15, MMm), (15, MMm + 1)]}
+
+
+def open_sides(cfg):
+    return [s for s, bit in OPEN.items() if cfg.obc & bit]
+
+
+def ub_arrays(cfg):
+    """Binding coefficients below 0, inside (0, 1) and above 1 on every edge, on the points 0:Mm+1 / 0:Lm+1."""
+    x = lambda n, ph: 0.5 + 1.5 * np.sin(np.arange(n) * 0.37 + ph)
+    return [x(cfg.MMm + 2, 0.0), x(cfg.MMm + 2, 1.0), x(cfg.LLm + 2, 2.0), x(cfg.LLm + 2, 3.0)]
+
+
+def lev(a, l, N):
+    return a[(l - 1) * N:l * N]
+
+
+def line(a, normal, c, m):
+    """a (.., Mm+4, Lm+4) on the line of normal index c ('x': i = c, 'y': j = c) at the along-edge indices m."""
+    return a[..., m + 1, c + 1] if normal == "x" else a[..., c + 1, m + 1]
+
+
+def build_twin(obc, LLm=TWIN_SIZE["LLm"], MMm=TWIN_SIZE["MMm"], N=TWIN_SIZE["N"]):
+    """(cfg, oracle, time indices, snapshot of every array the boundary routines touch) for the open sides obc.
+    flather_state at this size with seeded noise of the fields' own size on every time level, an offset on
+    u and v that differs between the time levels, land on one cell of every edge and a sign-changing wave
+    on the boundary velocities.  The snapshot is never written; callers restore the oracle from it."""
+    cfg, o, tix = flather_state(obc, LLm=LLm, MMm=MMm, N=N)
+    rng = np.random.default_rng(100 + obc)
+    for name in TWIN_STATE:
+        a = o.field(name)
+        amp = max(float(np.abs(a).max()), 0.05) * (0.1 if name == "t" else 1.0)
+        a += amp * rng.standard_normal(a.shape)
+        if name in ("u", "v"):
+            # a smooth offset that differs between the time levels: along every edge the change in time
+            # outweighs the gradients in places and not in others, so the cy clamp binds at both ends
+            J, I = np.meshgrid(np.arange(a.shape[-2]), np.arange(a.shape[-1]), indexing="ij")
+            for l in range(3):
+                lev(a, l + 1, cfg.N)[...] += 2.0 * amp * np.cos(2.1 * l + 0.15 * J + 0.1 * I)
+    rm = o.field("rmask")[0]
+    for side in twin_land(LLm, MMm).values():
+        for i, j in side:
+            rm[j + 1, i + 1] = 0.0
+    um, vm, pm_ = o.field("umask")[0], o.field("vmask")[0], o.field("pmask")[0]
+    um[:, 1:] = rm[:, 1:] * rm[:, :-1]
+    vm[1:, :] = rm[1:, :] * rm[:-1, :]
+    pm_[1:, 1:] = rm[1:, 1:] * rm[1:, :-1] * rm[:-1, 1:] * rm[:-1, :-1]
+    for name, m in (("zeta", rm), ("ubar", um), ("vbar", vm), ("u", um), ("v", vm), ("t", rm)):
+        o.field(name)[...] *= m
+    for q, side in enumerate(SIDES):                # boundary velocities of both signs, as cext_state
+        for comp in ("u", "v"):
+            a = o.field("%s_%s" % (comp, side)).reshape(cfg.N, -1)
+            m, k = np.arange(a.shape[1])[None, :], np.arange(cfg.N)[:, None]
+            a += 2.0 * max(float(np.abs(a).max()), 0.01) * np.sin(2.0 * np.pi * 3.0 * m / a.shape[1] + 0.4 * k + q)
+    snap = {n: o.field(n).copy() for n in TWIN_STATE + TWIN_MASKS + tuple(TWIN_BRY) + ("h", "pm", "pn")}
+    for a in snap.values():
+        a.setflags(write=False)
+    return cfg, o, tix, snap
+
+
+twin_state = functools.lru_cache(maxsize=None)(build_twin)      # one oracle per (obc, size), shared: restore before use
+
+
+def twin_restore(o, snap):
+    for n, a in snap.items():
+        o.field(n)[...] = a
+
+
+def all_taken(arms, where):
+    missing = [(where, k) for k, v in arms.items() if not bool(np.any(v))]
+    assert not missing, missing
+
+
+# The arm restatements read a dict S: the arrays handed to the routine under their field names, and
+# cfg, tix (iic, kstp, knew, nstp, nrhs, nnew) and ub (ub_arrays, or None for ub_tune off).
+def mask_arms(S, name, normal, c, m):
+    w = line(S[name][0], normal, c, m)
+    return {"wet edge point": w == 1.0, "dry edge point": w == 0.0}
+
+
+def ub_arms(S, side, m):
+    if S["ub"] is None:
+        return {}
+    b = S["ub"][SIDES.index(side)][m]
+    return {"ub < 0": b < 0.0, "0 < ub < 1": (b > 0.0) & (b < 1.0), "ub > 1": b > 1.0}
+
+
+def normal_arms(S, comp, side):
+    """Orlanski radiation of the normal component (u on west / east, v on south / north)."""
+    cfg, N = S["cfg"], S["cfg"].N
+    nstp, nnew = S["tix"][3], S["tix"][5]
+    normal, nal, nmax = ("x", cfg.MMm, cfg.LLm) if comp == "u" else ("y", cfg.LLm, cfg.MMm)
+    low = side in ("west", "south")
+    b, i1, i2 = (1, 2, 3) if low else (nmax + 1, nmax, nmax - 1)
+    m, m1 = np.arange(1, nal + 1), np.arange(1, nal + 2)
+    old, new = lev(S[comp], nstp, N), lev(S[comp], nnew, N)
+    gi = (line(old, normal, i1, m1) - line(old, normal, i1, m1 - 1)) * line(S["pmask"][0], normal, i1, m1)
+    dft = line(old, normal, i1, m) - line(new, normal, i1, m)
+    dfx = line(new, normal, i1, m) - line(new, normal, i2, m)
+    first = dft * (gi[:, :-1] + gi[:, 1:]) > 0.0
+    dfy = np.where(first, gi[:, :-1], gi[:, 1:])
+    cff = np.maximum(dfx * dfx + dfy * dfy, EPS)
+    raw = dft * dfy
+    inflow = dft * dfx < 0.0
+    data = S["%s_%s" % (comp, side)].reshape(N, -1)[:, 1:-1]
+    data_in = data > 0.0 if low else data < 0.0
+    arms = {"outflow": ~inflow, "inflow, boundary data bind": inflow & data_in, "inflow, ubind binds": inflow & ~data_in,
+            "first tangential gradient": first, "second tangential gradient": ~first,
+            "cy clamped at +cff": ~inflow & (raw > cff), "cy clamped at -cff": ~inflow & (raw < -cff),
+            "cy inside": ~inflow & (np.abs(raw) <= cff)}
+    arms.update(mask_arms(S, comp + "mask", normal, b, m))
+    arms.update(ub_arms(S, side, m))
+    return arms
+
+
+def tangential_arms(S, comp, side, fast=False):
+    """The tangential component (u on south / north, v on west / east): radiates for cx > 0, binds otherwise."""
+    cfg, N = S["cfg"], S["cfg"].N
+    normal, nal, nmax = ("y", cfg.LLm, cfg.MMm) if comp == "u" else ("x", cfg.MMm, cfg.LLm)
+    other = "v" if comp == "u" else "u"
+    low = side in ("west", "south")
+    m = np.arange(2, nal + 1)
+    if fast:
+        vel = S[other + "bar"][S["tix"][1] - 1]
+    else:
+        vel = lev(S[other], S["tix"][4], N)
+    c = 1 if low else nmax + 1
+    s = line(vel, normal, c, m) + line(vel, normal, c, m - 1)
+    cx_pos = (-s if low else s) > 0.0
+    arms = {"radiates (cx > 0)": cx_pos, "binds (cx <= 0)": ~cx_pos}
+    arms.update(mask_arms(S, comp + "mask", normal, 0 if low else nmax + 1, m))
+    if not fast:
+        arms.update(ub_arms(S, side, m))
+    return arms
+
+
+def tracer_arms(S, side):
+    cfg, N = S["cfg"], S["cfg"].N
+    normal, nal, nmax = ("x", cfg.MMm, cfg.LLm) if side in ("west", "east") else ("y", cfg.LLm, cfg.MMm)
+    low = side in ("west", "south")
+    m = np.arange(1, nal + 1)
+    vel = line(lev(S["u" if normal == "x" else "v"], S["tix"][4], N), normal, 1 if low else nmax + 1, m)
+    cx_pos = (-vel if low else vel) > 0.0
+    arms = {"radiates (cx > 0)": cx_pos, "binds (cx <= 0)": ~cx_pos}
+    arms.update(mask_arms(S, "rmask", normal, 0 if low else nmax + 1, m))
+    arms.update(ub_arms(S, side, m))
+    return arms
 
 
 # ------------------------------------------------------------------- KPP ----

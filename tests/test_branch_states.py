@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import branch_states as bs
+import oracle
 import romsgpu
 
 RESTATED = 1e-14
@@ -153,3 +154,39 @@ def test_kpp_layer_reaches_zero_short_wave(show):
     shares(show, "KPP mixed columns: hbls up to %.0f m;" % o.field("hbls")[0][bs.box(cfg)].max(), part)
     assert part["swr_frac(kbls-1) <= 0"] >= 0.05 and part["> 0"] >= 0.05
     all_finite(o)
+
+
+def _open_side_cases():
+    import test_gpu_open_sides as sweep
+    return sweep, sweep.SWEEP, sweep.SWEEP_IDS
+
+
+@pytest.mark.parametrize("obc,size", _open_side_cases()[1], ids=_open_side_cases()[2])
+def test_open_side_twin_takes_every_arm(obc, size):
+    """The oracle's half of tests/test_gpu_open_sides.py, for every set of open
+    sides at both sizes: the twin state takes every arm of step2d's and the
+    3-D routines' boundary code on every open side (asserted inside the
+    helpers), the oracle's outputs are finite, the sponge band lies along
+    the open sides alone, and in the 12-step run every open side moves and
+    every closed side stays a wall."""
+    sweep = _open_side_cases()[0]
+    sweep.stage(obc, size, "corr", False)
+    for iif in (1, 2):
+        sweep.oracle_step2d(obc, size, iif)
+    for routine, (mode, outs) in sweep.ROUTINES3D.items():
+        for tuned in (False, True):
+            cfg, o, tix, ub = sweep.oracle_3d_arms(obc, size, routine, tuned)
+            o.call(routine)
+            sweep.all_finite(o, outs)
+    cfg = bs.flather_cfg(obc, ndtfast=30, **sweep.size_kw(size))
+    cfg.v_sponge = sweep.V_SPONGE
+    o = oracle.Oracle(cfg)
+    o.init()
+    sweep.check_sponge(cfg, o)
+    cfg = sweep.run_cfg(obc, size)
+    o = oracle.Oracle(cfg)
+    o.init()
+    first = {n: o.field(n).copy() for n in sweep.STATE}
+    o.step(sweep.RUN_STEPS)
+    all_finite(o)
+    sweep.check_sides_moved(cfg, first, o.field)

@@ -24,8 +24,8 @@ switch variants.
 
 The OBC, SPONGE(_TUNE) and BULK_FRC branches of the oracle have no runnable
 golden log offline; they are pinned routine by routine to the reference's own
-code compiled beside stand-in modules (test_ref_pin_obc.py,
-test_ref_pin_bulk.py).  The CURVGRID momentum terms remain "parity unpinned"
+code compiled beside stand-in modules (test_ref_pin_obc.py for every set of
+open sides 1 .. 15, test_ref_pin_bulk.py).  The CURVGRID momentum terms remain "parity unpinned"
 (test_gpu_obc.py); everything else is pinned through the Filament / Pipes_ana
 goldens (test_oracle_golden.py).
 """

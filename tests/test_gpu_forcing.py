@@ -24,9 +24,9 @@ from test_gpu_register import host_model
 pytestmark = pytest.mark.gpu
 
 
-def open_basin(pot=1):
+def open_basin(pot=1, obc=15):
     c = basin_cfg(LLm=40, MMm=32, N=12, nonlin=True)
-    c.obc, c.ubind, c.pot_tides = 15, 0.1, pot
+    c.obc, c.ubind, c.pot_tides = obc, 0.1, pot
     o = oracle.Oracle(c)
     o.init()
     m, _ = host_model(o, c)

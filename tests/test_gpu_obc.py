@@ -12,9 +12,12 @@ available offline).  The oracle's open-boundary restatement
 reference routines themselves: zetabc, u2dbc_im, v2dbc_im, u3dbc_im, v3dbc_im,
 t3dbc_im and set_nudgcof compile unchanged beside stand-in modules
 (oracle/ref/build_ref.sh), and tests/test_ref_pin_obc.py holds the oracle to
-them bitwise for open sides 15, 5 and 10, predictor and corrector, ub_tune
-off and on, on states that take every data-dependent arm on every open side.
-So parity here, GPU vs oracle, means GPU vs reference for these routines.
+them bitwise for every non-empty set of open sides (1 .. 15), predictor and
+corrector, ub_tune off and on, on states that take every data-dependent arm
+on every open side.  So parity here, GPU vs oracle, means GPU vs reference
+for these routines.  This file runs the sides 15, 5 and 10;
+tests/test_gpu_open_sides.py runs all fifteen sets, so that every corner is
+seen between every pair of open and closed sides.
 The CURVGRID momentum terms (test_curvgrid_momentum_rhs_parity) stay "parity
 unpinned": they sit in the r.h.s. routines, which need more of the reference
 than the stand-ins give.  The closed-wall branches stay pinned by the

@@ -156,15 +156,22 @@ def _gpu_case(kind):
         return c
     if kind == "basin_obc":   # open edges (LapT copies at the edges) and an island (masks)
         return iso_cfg(LLm=40, MMm=32, N=16, obc=15, island=1)
+    if kind.startswith("basin_obc"):   # basin_obc6 (east + south open), basin_obc9 (west + north): LapT copied on
+        # two sides and zero on the other two, each corner between a different pair (k_iso.hip)
+        return iso_cfg(LLm=40, MMm=32, N=16, obc=int(kind[len("basin_obc"):]), island=1)
     return iso_cfg(LLm=40, MMm=32, N=16)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["basin", "basin_obc", "filament"])
+@pytest.mark.parametrize("kind", ["basin", "basin_obc", "basin_obc6", "basin_obc9", "filament"])
 def test_gpu_iso_steps_match_oracle(kind):
     """One whole step within 1e-12 (relative to each field's max, interior; the
     per-routine bound), then 20 steps within the north_star RMS bound,
-    ADV_ISONEUTRAL on in both."""
+    ADV_ISONEUTRAL on in both.  basin_obc6 and basin_obc9 open two sides only,
+    so that every side runs the LapT edge copy and the zero of a closed edge,
+    and every corner lies between one of each.  These ISO edge copies remain
+    unpinned to the reference, as the rest of the operator (see above): the
+    oracle is the only yardstick for them."""
     from test_gpu_parity import PROGNOSTIC, RMS_RUN, check_fields
     cfg = _gpu_case(kind)
     o = oracle.Oracle(cfg)

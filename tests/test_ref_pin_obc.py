@@ -4,7 +4,9 @@ oracle/ref/build_ref.sh compiles zetabc_tile, u2dbc_tile, v2dbc_tile,
 u3dbc_tile, v3dbc_tile, t3dbc_tile and set_nudgcof from the reference tree,
 unchanged, for the Iceland boundary switch set (OBC_M2FLATHER, OBC_M3ORLANSKI,
 OBC_TORLANSKI, *_FRC_BRY, SPONGE, SPONGE_TUNE, MASKING) at 24 x 20 x 6 with
-open sides 15, 5 and 10.  Each test hands one state to the reference routine
+every non-empty set of open sides, 1 .. 15 (bits 1 W, 2 E, 4 S, 8 N), so that
+each of the four corners is seen open-open, open on one side only (either
+one) and closed-closed.  Each test hands one state to the reference routine
 and to its restatement in oracle/oracle_obc.c (or_set_nudgcof in
 oracle_main.c) and compares every element of every array the routine can
 write, ghost rows and corners included.
@@ -13,8 +15,8 @@ Agreement is bitwise: the routines use + - * / sqrt min max in IEEE double,
 both sides are built without contraction, so any difference is a difference
 in the order of evaluation or in the arm taken.  No tolerance.
 
-The state is a perturbed twin of a mid-run state (branch_states.flather_state
-at the library's size): seeded noise of the fields' own size on every time
+The state is a perturbed twin of a mid-run state (branch_states.twin_state:
+flather_state at the library's size): seeded noise of the fields' own size on every time
 level, a sign-changing wave on the boundary velocities, land on one cell of
 every edge, binding coefficients below 0, inside (0, 1) and above 1.  From the
 arrays handed to the reference each test restates the data-dependent branch
@@ -27,7 +29,6 @@ Not marked gpu.  Skips only where neither the libraries nor the reference
 tree exist.
 """
 import ctypes
-import functools
 
 import numpy as np
 import pytest
@@ -36,14 +37,14 @@ import branch_states as bs
 import oracle
 import oracle.ref as ref
 
-SIZE = dict(LLm=24, MMm=20, N=6)
-EPS = 1.0e-33
-OPEN = {"west": 1, "east": 2, "south": 4, "north": 8}
-STATE = ("zeta", "ubar", "vbar", "u", "v", "t")
-MASKS = ("rmask", "umask", "vmask", "pmask")
-BRY = ["%s_%s" % (v, e) for v in STATE for e in ref.SIDES]
-# one land cell on every edge, with its ghost neighbour: (i, j) in Fortran indices
-LAND = {"west": [(0, 7), (1, 7)], "east": [(24, 11), (25, 11)], "south": [(9, 0), (9, 1)], "north": [(15, 20), (15, 21)]}
+SIZE = bs.TWIN_SIZE
+OPEN = bs.OPEN
+STATE = bs.TWIN_STATE
+# the twin state and the arm restatements live in branch_states, shared with tests/test_gpu_open_sides.py
+ub_arrays, restore, open_sides, all_taken = bs.ub_arrays, bs.twin_restore, bs.open_sides, bs.all_taken
+mask_arms, ub_arms, normal_arms, tangential_arms, tracer_arms = (bs.mask_arms, bs.ub_arms, bs.normal_arms,
+                                                                 bs.tangential_arms, bs.tracer_arms)
+CORNERS = (("west", "south"), ("east", "south"), ("west", "north"), ("east", "north"))
 
 pytestmark = pytest.mark.skipif(not (ref.have_tree() or all(ref.available(v) for v in ref.VARIANTS)),
                                 reason="neither oracle/_ref libraries nor a reference tree")
@@ -57,52 +58,10 @@ def same(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
-def ub_arrays(cfg):
-    """Binding coefficients below 0, inside (0, 1) and above 1 on every edge, on the points 0:Mm+1 / 0:Lm+1."""
-    x = lambda n, ph: 0.5 + 1.5 * np.sin(np.arange(n) * 0.37 + ph)
-    return [x(cfg.MMm + 2, 0.0), x(cfg.MMm + 2, 1.0), x(cfg.LLm + 2, 2.0), x(cfg.LLm + 2, 3.0)]
-
-
-@functools.lru_cache(maxsize=None)
 def twin(obc):
     """(cfg, oracle, time indices, snapshot of every array the tests touch).  The snapshot is never written."""
     assert ref.available(obc)
-    cfg, o, tix = bs.flather_state(obc, **SIZE)
-    rng = np.random.default_rng(100 + obc)
-    for name in STATE:
-        a = o.field(name)
-        amp = max(float(np.abs(a).max()), 0.05) * (0.1 if name == "t" else 1.0)
-        a += amp * rng.standard_normal(a.shape)
-        if name in ("u", "v"):
-            # a smooth offset that differs between the time levels: along every edge the change in time
-            # outweighs the gradients in places and not in others, so the cy clamp binds at both ends
-            J, I = np.meshgrid(np.arange(a.shape[-2]), np.arange(a.shape[-1]), indexing="ij")
-            for l in range(3):
-                lev(a, l + 1, cfg.N)[...] += 2.0 * amp * np.cos(2.1 * l + 0.15 * J + 0.1 * I)
-    rm = o.field("rmask")[0]
-    for side in LAND.values():
-        for i, j in side:
-            rm[j + 1, i + 1] = 0.0
-    um, vm, pm_ = o.field("umask")[0], o.field("vmask")[0], o.field("pmask")[0]
-    um[:, 1:] = rm[:, 1:] * rm[:, :-1]
-    vm[1:, :] = rm[1:, :] * rm[:-1, :]
-    pm_[1:, 1:] = rm[1:, 1:] * rm[1:, :-1] * rm[:-1, 1:] * rm[:-1, :-1]
-    for name, m in (("zeta", rm), ("ubar", um), ("vbar", vm), ("u", um), ("v", vm), ("t", rm)):
-        o.field(name)[...] *= m
-    for q, side in enumerate(ref.SIDES):           # boundary velocities of both signs, as bs.cext_state
-        for comp in ("u", "v"):
-            a = o.field("%s_%s" % (comp, side)).reshape(cfg.N, -1)
-            m, k = np.arange(a.shape[1])[None, :], np.arange(cfg.N)[:, None]
-            a += 2.0 * max(float(np.abs(a).max()), 0.01) * np.sin(2.0 * np.pi * 3.0 * m / a.shape[1] + 0.4 * k + q)
-    snap = {n: o.field(n).copy() for n in STATE + MASKS + tuple(BRY) + ("h", "pm", "pn")}
-    for a in snap.values():
-        a.setflags(write=False)
-    return cfg, o, tix, snap
-
-
-def restore(o, snap):
-    for n, a in snap.items():
-        o.field(n)[...] = a
+    return bs.twin_state(obc, **SIZE)
 
 
 def setup(obc, mode, tuned):
@@ -130,108 +89,23 @@ def compare(o, r, snap, wrote):
         corners_written(o.cfg, n, out[n], snap[n])
 
 
-def corners_written(cfg, name, out, snap):
-    """The routine wrote the corner points it owns: those between two open sides for the velocities
-    (u2dbc_im.F:455-478 and its twins), all four for zeta and the tracers."""
+def corner_points(cfg, name):
+    """(E/W side, N/S side, i, j) of the four corner points of the field, Fortran indices."""
     L, M = cfg.LLm, cfg.MMm
     lo = {"u": (1, 0), "ubar": (1, 0), "v": (0, 1), "vbar": (0, 1)}.get(name, (0, 0))
-    for ew, ns, i, j in (("west", "south", lo[0], lo[1]), ("east", "south", L + 1, lo[1]),
-                         ("west", "north", lo[0], M + 1), ("east", "north", L + 1, M + 1)):
-        both_open = bool(cfg.obc & OPEN[ew]) and bool(cfg.obc & OPEN[ns])
-        if both_open or name in ("zeta", "t"):
-            assert not same(out[..., j + 1, i + 1], snap[..., j + 1, i + 1]), (name, ew, ns)
+    return (("west", "south", lo[0], lo[1]), ("east", "south", L + 1, lo[1]),
+            ("west", "north", lo[0], M + 1), ("east", "north", L + 1, M + 1))
 
 
-def open_sides(cfg):
-    return [s for s, bit in OPEN.items() if cfg.obc & bit]
-
-
-def line(a, normal, c, m):
-    """a (.., Mm+4, Lm+4) on the line of normal index c ('x': i = c, 'y': j = c) at the along-edge indices m."""
-    return a[..., m + 1, c + 1] if normal == "x" else a[..., c + 1, m + 1]
-
-
-def lev(a, l, N):
-    return a[(l - 1) * N:l * N]
-
-
-def all_taken(arms, where):
-    missing = [(where, k) for k, v in arms.items() if not bool(np.any(v))]
-    assert not missing, missing
-
-
-def mask_arms(S, name, normal, c, m):
-    w = line(S[name][0], normal, c, m)
-    return {"wet edge point": w == 1.0, "dry edge point": w == 0.0}
-
-
-def ub_arms(S, side, m):
-    if S["ub"] is None:
-        return {}
-    b = S["ub"][ref.SIDES.index(side)][m]
-    return {"ub < 0": b < 0.0, "0 < ub < 1": (b > 0.0) & (b < 1.0), "ub > 1": b > 1.0}
-
-
-def normal_arms(S, comp, side):
-    """Orlanski radiation of the normal component (u on west / east, v on south / north)."""
-    cfg, N = S["cfg"], S["cfg"].N
-    nstp, nnew = S["tix"][3], S["tix"][5]
-    normal, nal, nmax = ("x", cfg.MMm, cfg.LLm) if comp == "u" else ("y", cfg.LLm, cfg.MMm)
-    low = side in ("west", "south")
-    b, i1, i2 = (1, 2, 3) if low else (nmax + 1, nmax, nmax - 1)
-    m, m1 = np.arange(1, nal + 1), np.arange(1, nal + 2)
-    old, new = lev(S[comp], nstp, N), lev(S[comp], nnew, N)
-    gi = (line(old, normal, i1, m1) - line(old, normal, i1, m1 - 1)) * line(S["pmask"][0], normal, i1, m1)
-    dft = line(old, normal, i1, m) - line(new, normal, i1, m)
-    dfx = line(new, normal, i1, m) - line(new, normal, i2, m)
-    first = dft * (gi[:, :-1] + gi[:, 1:]) > 0.0
-    dfy = np.where(first, gi[:, :-1], gi[:, 1:])
-    cff = np.maximum(dfx * dfx + dfy * dfy, EPS)
-    raw = dft * dfy
-    inflow = dft * dfx < 0.0
-    data = S["%s_%s" % (comp, side)].reshape(N, -1)[:, 1:-1]
-    data_in = data > 0.0 if low else data < 0.0
-    arms = {"outflow": ~inflow, "inflow, boundary data bind": inflow & data_in, "inflow, ubind binds": inflow & ~data_in,
-            "first tangential gradient": first, "second tangential gradient": ~first,
-            "cy clamped at +cff": ~inflow & (raw > cff), "cy clamped at -cff": ~inflow & (raw < -cff),
-            "cy inside": ~inflow & (np.abs(raw) <= cff)}
-    arms.update(mask_arms(S, comp + "mask", normal, b, m))
-    arms.update(ub_arms(S, side, m))
-    return arms
-
-
-def tangential_arms(S, comp, side, fast=False):
-    """The tangential component (u on south / north, v on west / east): radiates for cx > 0, binds otherwise."""
-    cfg, N = S["cfg"], S["cfg"].N
-    normal, nal, nmax = ("y", cfg.LLm, cfg.MMm) if comp == "u" else ("x", cfg.MMm, cfg.LLm)
-    other = "v" if comp == "u" else "u"
-    low = side in ("west", "south")
-    m = np.arange(2, nal + 1)
-    if fast:
-        vel = S[other + "bar"][S["tix"][1] - 1]
-    else:
-        vel = lev(S[other], S["tix"][4], N)
-    c = 1 if low else nmax + 1
-    s = line(vel, normal, c, m) + line(vel, normal, c, m - 1)
-    cx_pos = (-s if low else s) > 0.0
-    arms = {"radiates (cx > 0)": cx_pos, "binds (cx <= 0)": ~cx_pos}
-    arms.update(mask_arms(S, comp + "mask", normal, 0 if low else nmax + 1, m))
-    if not fast:
-        arms.update(ub_arms(S, side, m))
-    return arms
-
-
-def tracer_arms(S, side):
-    cfg, N = S["cfg"], S["cfg"].N
-    normal, nal, nmax = ("x", cfg.MMm, cfg.LLm) if side in ("west", "east") else ("y", cfg.LLm, cfg.MMm)
-    low = side in ("west", "south")
-    m = np.arange(1, nal + 1)
-    vel = line(lev(S["u" if normal == "x" else "v"], S["tix"][4], N), normal, 1 if low else nmax + 1, m)
-    cx_pos = (-vel if low else vel) > 0.0
-    arms = {"radiates (cx > 0)": cx_pos, "binds (cx <= 0)": ~cx_pos}
-    arms.update(mask_arms(S, "rmask", normal, 0 if low else nmax + 1, m))
-    arms.update(ub_arms(S, side, m))
-    return arms
+def corners_written(cfg, name, out, snap):
+    """The routine wrote the corner points it owns: those between two open sides for the velocities
+    (u2dbc_im.F:455-478 and its twins), all four for zeta and the tracers -- the mixed corners, between
+    an open and a closed side, among them."""
+    for ew, ns, i, j in corner_points(cfg, name):
+        o_ew, o_ns = bool(cfg.obc & OPEN[ew]), bool(cfg.obc & OPEN[ns])
+        kind = "open-open" if o_ew and o_ns else "mixed" if o_ew or o_ns else "closed-closed"
+        if kind == "open-open" or name in ("zeta", "t"):
+            assert not same(out[..., j + 1, i + 1], snap[..., j + 1, i + 1]), (name, ew, ns, kind)
 
 
 def check_metrics(S):
@@ -241,15 +115,20 @@ def check_metrics(S):
 CASES3D = [(obc, mode, tuned) for obc in ref.VARIANTS for mode in ("pred", "corr") for tuned in (False, True)]
 
 
-def test_libraries_cover_both_corner_kinds():
-    """Open-open corners with sides 15, open-closed and closed-closed with 5 and 10; the sizes are what the tests assume."""
-    kinds = set()
+def test_libraries_cover_every_kind_at_every_corner():
+    """Each of the four corners, which have hand-written lines of their own in every boundary routine, sees
+    all four kinds across the libraries: open-open, E/W open only, N/S open only, closed-closed.  The sizes
+    are what the tests assume."""
+    kinds = {c: set() for c in CORNERS}
     for obc in ref.VARIANTS:
         r = ref.RefLib(obc)
         assert (r.LLm, r.MMm, r.N, r.NT) == (SIZE["LLm"], SIZE["MMm"], SIZE["N"], 2) and r.LLm != r.MMm
-        for ew, ns in ((1, 4), (2, 4), (1, 8), (2, 8)):
-            kinds.add((bool(obc & ew), bool(obc & ns)))
-    assert kinds == {(True, True), (True, False), (False, True), (False, False)}
+        assert r.obc == obc
+        for ew, ns in CORNERS:
+            kinds[(ew, ns)].add((bool(obc & OPEN[ew]), bool(obc & OPEN[ns])))
+    every = {(True, True), (True, False), (False, True), (False, False)}
+    short = {c: sorted(every - k) for c, k in kinds.items() if k != every}
+    assert not short, short
 
 
 @pytest.mark.parametrize("obc", ref.VARIANTS)
