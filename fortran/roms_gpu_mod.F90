@@ -58,7 +58,12 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 28 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 29 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
+  integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
+                               ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
+                               ROMS_WRT_AKT = 512, ROMS_WRT_AKS = 1024, ROMS_WRT_HBLS = 2048, ROMS_WRT_HBBL = 4096, &
+                               ROMS_WRT_W = 8192, ROMS_WRT_DEFAULT = 63
   ! extraction variables (ROMS_EXT_*); UP, VP, W, BGC are parsed and reported, not produced
   integer(c_int), parameter :: ROMS_EXT_ZETA = 1, ROMS_EXT_UBAR = 2, ROMS_EXT_VBAR = 4, ROMS_EXT_U = 8, &
                                ROMS_EXT_V = 16, ROMS_EXT_TEMP = 32, ROMS_EXT_SALT = 64, ROMS_EXT_UP = 128, &
@@ -308,6 +313,22 @@ module roms_gpu_mod
       integer(c_int), value :: n
       type(roms_tlev), intent(in) :: t
       real(c_double), intent(out) :: ms
+    end function
+    ! true vertical velocity (k_wvlcty.hip): wvlcty_tile of wvlcty.F
+    integer(c_int) function roms_gpu_wvlcty(t) bind(c)
+      import :: c_int, roms_tlev
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_wvlcty_copy_out(dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_time_wvlcty(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(in) :: t
+      real(c_double), intent(out) :: ms(2)
     end function
     ! z-level slices (k_zslice.hip): calc_zslice / wrt_zslice of zslice_output.F
     integer(c_int) function roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg) bind(c)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 28
+#define ROMS_GPU_ABI_VERSION 29
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -546,7 +546,9 @@ int roms_gpu_set_tides(double time);
 #define ROMS_WRT_AKS  1024
 #define ROMS_WRT_HBLS 2048
 #define ROMS_WRT_HBBL 4096
-#define ROMS_WRT_DEFAULT 63  /* ocean_vars.opt defaults: Z, Ub, Vb, U, V + tracers */
+#define ROMS_WRT_W    8192   /* true vertical velocity w at rho points, m/s (wvlcty.F; wrt_W, wrt_avg_W) */
+#define ROMS_WRT_DEFAULT 63  /* Z, Ub, Vb, U, V + tracers; the callers choose the rest (ocean_vars.opt also
+                                sets wrt_avg_W: an averages file like the reference's default arms ROMS_WRT_W) */
 int roms_gpu_wrt_rst(const char *path, int rec, int total_rec, double time, const roms_tlev *t);
 int roms_gpu_wrt_his(const char *path, int rec, int total_rec, double time, const roms_tlev *t, int wrt_mask);
 int roms_gpu_io_wait(void);
@@ -564,7 +566,8 @@ int roms_gpu_io_wait(void);
  * whatever the mask and NT): navg += 1, coef = 1/navg,
  *   t_avg = t_avg*(1-coef) + time*coef,  X_avg = X_avg*(1-coef) + X*coef
  * with X = zeta/ubar/vbar(t->knew), u/v/tracers(t->nstp), rho1 - qp1*z_r
- * (SPLIT_EOS) or rho, We + Wi, Akv, Akt(itemp), Akt(isalt), hbls, hbbl.
+ * (SPLIT_EOS) or rho, We + Wi, Akv, Akt(itemp), Akt(isalt), hbls, hbbl, and w
+ * (ROMS_WRT_W, ABI 29, below: a second launch).
  * u, v and the tracers are sampled in slot nstp, NOT nnew: after a step nstp
  * holds time n while zeta(knew) and `time` are at n+1 -- the reference's
  * choice, kept for parity of the files.  The state at t = 0 is never sampled.
@@ -593,6 +596,48 @@ int roms_gpu_wrt_avg(const char *path, int rec, int total_rec, double period, co
 int roms_gpu_avg_state(int *navg, double *t_avg, int *mask);
 int roms_gpu_avg_copy_out(int wrt_bit, int itrc, double *dst, long count);
 int roms_gpu_time_calc_avg(int n, const roms_tlev *t, double *ms);
+/* ---- true vertical velocity on the device (ABI 29): wvlcty_tile of wvlcty.F.
+ * w at rho points and rho levels, m/s: Wrk(0) = 0, Wrk(k) = Wrk(k-1) -
+ * pm*pn*(FlxU(i+1)-FlxU(i)+FlxV(j+1)-FlxV(j)) (no grid-motion term: Wrk(N) is
+ * not 0, unlike omega), interpolated to rho levels with the four-point weights
+ * and one-sided ends, plus 0.25*(Wxi(i)+Wxi(i+1)+Weta(j)+Weta(j+1)) with
+ * Wxi(i) = u(i,t->nstp)*(z_r(i)-z_r(i-1))*(pm(i)+pm(i-1)) and Weta alike in j
+ * -- slot nstp whatever the caller then writes for u itself -- over
+ * istr..iend x jstr..jend, one row more on each side in a periodic direction
+ * only; gradient copies onto physical edges and corners; no mask multiply.
+ * FlxU, FlxV, u and v(nstp) are the arrays as roms_gpu_copy_out returns them
+ * (whole steps always store them); z_r is the stored array, or formed from the
+ * kept free surface while the stored grid is set_depth's own (the same bits).
+ * N < 2 has no formula (the top level needs Wrk(N-2)): every entry that would
+ * compute w then returns -1 with a message.
+ * roms_gpu_wvlcty fills a device work array of N planes (allocated on first
+ * use; freed by roms_gpu_finalize and by roms_gpu_avg_begin with mask 0) on
+ * the library stream.  roms_gpu_wvlcty_copy_out returns it as (N, Mm+4, Lm+4)
+ * in the host layout of a rho field (count must be that size; cells outside
+ * the computed range and its copies hold 0), -4 if nothing was computed.
+ * roms_gpu_time_wvlcty: n launches per sink between two events on the library
+ * stream, total milliseconds: ms[0] the store into the work array, ms[1] the
+ * running-mean sink with the old mean read (0 unless ROMS_WRT_W is armed; the
+ * mean it advances is then no average of anything: re-arm before use).
+ * roms_gpu_wrt_his with ROMS_WRT_W computes w into the work array ahead of the
+ * snapshot and writes variable w ('vertical velocity', meter second-1, on
+ * (time, s_rho, eta_rho, xi_rho), levels 1:N over i0:i1, j0:j1) between omega
+ * and AKv, where def_vars_ocean_vars defines it.  roms_gpu_avg_begin with
+ * ROMS_WRT_W (accepted in every configuration, never dropped) allocates its
+ * running mean; every roms_gpu_calc_avg then samples it with one launch of its
+ * own (the other fields keep their single launch): the kernel that computes w
+ * applies avg = avg*(1-coef) + w*coef in the same lane, over exactly the cells
+ * it computes or copies, without the old mean's load at coef == 1.
+ * roms_gpu_wrt_avg writes it as w, 'averaged vertical velocity', and
+ * roms_gpu_avg_copy_out serves it under ROMS_WRT_W with N levels.
+ * Extraction objects still report 'w' as unsupported: the reference hands
+ * extract_data a Wvl(..,nz+1) array through a dummy declared (..,0:N) and
+ * interpolates levels 0..N-1 of it, level 0 never written, over halo cells no
+ * exchange fills (extract_data.F:204, 707-718) -- there is no defined answer
+ * to match.                                                                  */
+int roms_gpu_wvlcty(const roms_tlev *t);
+int roms_gpu_wvlcty_copy_out(double *dst, long count);
+int roms_gpu_time_wvlcty(int n, const roms_tlev *t, double *ms);
 /* ---- z-level slices on the device (ABI 26): calc_zslice / sigma_to_z /
  * calc_average / wrt_zslice of zslice_output.F.  u, v and chosen tracers, slot
  * t->nnew (the slot roms_gpu_wrt_his samples), interpolated from the model
@@ -669,7 +714,7 @@ int roms_gpu_time_calc_zslice(int n, const roms_tlev *t, double *ms);
  * 'grid1', '_west'); a variable is called set_var+bnd.  output_vars is
  * searched for substrings as findstr does: 'zeta', 'temp', 'salt', 'ubar',
  * 'vbar', 'u' (also found in 'ubar' and 'up'), 'v', 'w', 'up', 'vp', 'bgc'.
- * ROMS_EXT_UP/VP/W/BGC are not produced (no calc_pflx, wvlcty, BGC here):
+ * ROMS_EXT_UP/VP/W/BGC are not produced (no calc_pflx or BGC here; w: see ABI 29 above):
  * they are reported in the object's `unsupported` mask and named in
  * roms_gpu_last_error while the call returns 0.  'salt' is ignored without
  * SALINITY.  Refused (-1, nothing armed): a vector variable on a scalar

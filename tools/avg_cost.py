@@ -11,8 +11,11 @@ one box, one session:
 
 Algorithmic bytes of one sample: 3 passes per plain field (source read, old
 mean read, new mean written), 5 for rho under SPLIT_EOS (rho1, qp1, z_r), 4
-for omega (We, Wi), over interior cells as bench.py counts them; the
-coef == 1 saving is left out.
+for omega (We, Wi), 6 for w (ROMS_WRT_W: FlxU, FlxV, u, v, old mean, new mean,
+a launch of k_wvlcty of its own; tools/wvlcty_cost.py times it alone), over
+interior cells as bench.py counts them; the coef == 1 saving is left out.
+"Full mask" is romsgpu.WRT_ALL, which holds w since ABI 29: figures recorded
+before that (profiles/avg_cost.txt) are without it.
 
 usage: python tools/avg_cost.py [--samples 20] [--steps 10] [--no-membw]
 """
@@ -50,6 +53,7 @@ def sample_bytes(mask, I, J, N, NT):
     b += 3 * c3 * NT if mask & W["T"] else 0.0
     b += 5 * c3 if mask & W["R"] else 0.0
     b += 4 * c3w if mask & W["O"] else 0.0
+    b += 6 * c3 if mask & W.get("W", 0) else 0.0
     for k in ("Akv", "Akt", "Aks"):
         b += 3 * c3w if mask & W[k] else 0.0
     return b

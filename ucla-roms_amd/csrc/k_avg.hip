@@ -4,7 +4,8 @@
 //   navg = navg + 1;  coef = 1/navg;  X_avg = X_avg*(1-coef) + X*coef
 // with X = zeta/ubar/vbar(knew), u/v/t(nstp) -- slot nstp, which holds time n
 // after the step, as the reference samples it -- rho1 - qp1*z_r (SPLIT_EOS) or
-// rho, We + Wi, Akv, Akt(itemp), Akt(isalt), hbls, hbbl.
+// rho, We + Wi, Akv, Akt(itemp), Akt(isalt), hbls, hbbl; the true vertical
+// velocity w (ROMS_WRT_W) is sampled by k_wvlcty.hip's running-mean sink.
 //
 // MI355X design: a pure stream.  The average of a field has the device layout
 // of one slot of that field (same row pitch, same plane stride, same
@@ -152,12 +153,18 @@ unsigned avg_blocks(long nmax) {
 int avg_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) {
   const Bounds& b = S.d->b;
   const long ok = (long)(t.knew - 1) * b.n2, on = (long)(t.nstp - 1) * b.n3;
-  const dim3 grid(avg_blocks(A.nmax), (unsigned)A.fields.size());
+  const dim3 grid(avg_blocks(A.nmax), (unsigned)(A.fields.empty() ? 1 : A.fields.size()));
   // AKs samples Akt(isalt), which whole steps may leave unformed (shim_akt_sync)
   if ((A.v.mask & ROMS_WRT_AKS) && shim_akt_sync() != hipSuccess) return -3;
-  if (coef == 1.0) hipLaunchKernelGGL(k_calc_avg<true>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
-  else hipLaunchKernelGGL(k_calc_avg<false>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  if (!A.fields.empty()) {
+    if (coef == 1.0) hipLaunchKernelGGL(k_calc_avg<true>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
+    else hipLaunchKernelGGL(k_calc_avg<false>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
+    if (hipGetLastError() != hipSuccess) return -3;
+  }
+  // w (wvlcty.F) is a launch of its own: k_wvlcty with the running mean as its sink, over the cells it
+  // computes or copies (k_wvlcty.hip)
+  if (A.v.wvl) return wvl_launch(S, t.nstp, A.v.wvl, coef == 1.0 ? kWvlMeanFirst : kWvlMean, coef, cm1);
+  return 0;
 }
 
 bool tlev_ok(const roms_tlev* t) { return t && t->knew >= 1 && t->knew <= 4 && t->nstp >= 1 && t->nstp <= 3; }
@@ -183,11 +190,15 @@ int roms_gpu_avg_begin(int wrt_mask) {
   const Bounds& b = S.d->b;
   const Fields& F = S.d->f;
   const int all = ROMS_WRT_Z | ROMS_WRT_UB | ROMS_WRT_VB | ROMS_WRT_U | ROMS_WRT_V | ROMS_WRT_T | ROMS_WRT_R | ROMS_WRT_O |
-                  ROMS_WRT_AKV | ROMS_WRT_AKT | ROMS_WRT_AKS | ROMS_WRT_HBLS | ROMS_WRT_HBBL;
+                  ROMS_WRT_AKV | ROMS_WRT_AKT | ROMS_WRT_AKS | ROMS_WRT_HBLS | ROMS_WRT_HBBL | ROMS_WRT_W;
   int mask = wrt_mask & all;
   if (!S.cfg->salinity) mask &= ~ROMS_WRT_AKS;
   if (!S.cfg->lmd_mixing) mask &= ~(ROMS_WRT_HBLS | ROMS_WRT_HBBL);
-  if (!mask) return 0;   // disarmed
+  if (!mask) { wvl_free(); return 0; }   // disarmed
+  if ((mask & ROMS_WRT_W) && b.N < 2) {
+    *S.err = "roms_gpu_avg_begin: ROMS_WRT_W needs N >= 2 (wvlcty.F has no formula below)";
+    return -1;
+  }
   bool oom = false;
   auto add = [&](double*& dst, const double* a, long n, int kind, int slot, const double* bb = nullptr,
                  const double* cc = nullptr) {
@@ -216,7 +227,15 @@ int roms_gpu_avg_begin(int wrt_mask) {
   if (!oom && (mask & ROMS_WRT_AKS)) add(V.aks, F.Akt + b.n3w, b.n3w, kAvgCopy, kSlotNone);
   if (!oom && (mask & ROMS_WRT_HBLS)) add(V.hbls, F.hbls, b.n2, kAvgCopy, kSlotNone);
   if (!oom && (mask & ROMS_WRT_HBBL)) add(V.hbbl, F.hbbl, b.n2, kAvgCopy, kSlotNone);
-  if (!oom) {
+  if (!oom && (mask & ROMS_WRT_W)) {   // not in the table: sampled by k_wvlcty itself
+    AvgBuf wb;
+    V.wvl = wvl_alloc_like_u(*S.d, S.s, &wb.base);
+    wb.p = V.wvl;
+    wb.n = b.n3;
+    if (V.wvl) A.bufs.push_back(wb);
+    else oom = true;
+  }
+  if (!oom && !A.fields.empty()) {
     const size_t bytes = A.fields.size() * sizeof(AvgField);
     oom = hipMalloc(&A.d_tab, bytes) != hipSuccess ||
           copy_on(A.d_tab, A.fields.data(), bytes, hipMemcpyHostToDevice, S.s) != hipSuccess;
@@ -280,6 +299,7 @@ int roms_gpu_avg_copy_out(int wrt_bit, int itrc, double* dst, long count) {
     case ROMS_WRT_AKS: p = V.aks; levels = N + 1; break;
     case ROMS_WRT_HBLS: p = V.hbls; break;
     case ROMS_WRT_HBBL: p = V.hbbl; break;
+    case ROMS_WRT_W: p = V.wvl; levels = N; break;
     default: *S.err = "roms_gpu_avg_copy_out: wrt_bit must be one ROMS_WRT_* bit"; return -1;
   }
   const long rows = (long)levels * (S.d->b.Mm + 4), hcount = rows * (S.d->b.Lm + 4);

@@ -423,6 +423,7 @@ hipError_t dev_alloc(double*& p, long n) {
 void free_all() {
   io_free();
   avg_free();
+  wvl_free();
   zslice_free();
   extract_free();
   frc_free();

@@ -203,7 +203,8 @@ void global_atts(nc::File& f, const ShimState& S, const char* type) {
 // the variable list of a restart (def_vars_rst_ocean_vars), history or, with
 // av, averages record (def_vars_ocean_vars(.true.): the running means of
 // k_avg.hip in place of the fields, 'averaged ' ahead of every long name)
-std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst, int mask, const AvgView* av = nullptr) {
+std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst, int mask, const AvgView* av = nullptr,
+                                const double* wvl = nullptr) {
   const Bounds& b = S.d->b;
   const Fields& F = S.d->f;
   const Part p = part_of(*S.dims);
@@ -253,6 +254,9 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
     o.pm = F.pm + off;
     o.pn = F.pn + off;
   }
+  // true vertical velocity (wvlcty.F; basic_output.F:386-392, 486, defined :816-822 between omega and AKv):
+  // history takes the work array write_record filled just before, averages the running mean
+  if (!rst && (mask & ROMS_WRT_W) && (av ? av->wvl : wvl)) add("w", "vertical velocity", "meter second-1", 'r', N, av ? av->wvl : wvl, n2);
   if (!rst && (mask & ROMS_WRT_AKV)) add("AKv", "vertical viscosity coefficient", "meter2 second-1", 'r', N + 1, av ? av->akv : F.Akv, n2);
   if (!rst && (mask & ROMS_WRT_AKT))
     add("AKt", "temperature vertical diffusion coefficient", "meter2 second-1", 'r', N + 1, av ? av->akt : F.Akt, n2);
@@ -351,7 +355,13 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
     time = av->t_avg;
   }
   if ((r = io_join(*S.err))) return r;
-  std::vector<OutVar> vars = zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av);
+  const double* wvl = nullptr;
+  if (!rst && !avg && !zv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
+    if (t->nstp < 1 || t->nstp > 3) { *S.err = "roms_gpu_wrt_his: bad time levels"; return -1; }
+    wvl = wvl_compute(S, t->nstp, &r);
+    if (r) return r;
+  }
+  std::vector<OutVar> vars = zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av, wvl);
   size_t n = 0;
   for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
   if (!io.drain) {

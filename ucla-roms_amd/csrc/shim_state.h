@@ -64,11 +64,21 @@ struct AvgView {
   double t_avg = 0.0;  // their mean time
   double *zeta = nullptr, *ubar = nullptr, *vbar = nullptr, *u = nullptr, *v = nullptr, *rho = nullptr, *w = nullptr,
          *akv = nullptr, *akt = nullptr, *aks = nullptr, *hbls = nullptr, *hbbl = nullptr;
+  double* wvl = nullptr;    // true vertical velocity (ROMS_WRT_W), N levels in u's layout; sampled by k_wvlcty's mean sink
   std::vector<double*> t;   // one per tracer
 };
 const AvgView& avg_view();
 void avg_window_written();   // wrt_avg: navg = 0, the next sample starts a fresh window
 void avg_free();             // roms_gpu_finalize
+// True vertical velocity (k_wvlcty.hip): one kernel body, three sinks
+enum WvlSink : int { kWvlStore = 0, kWvlMean = 1, kWvlMeanFirst = 2 };   // work array | avg*cm1 + w*coef | w*coef, no load
+// one launch over wvlcty_tile's range from FlxU, FlxV, u, v(nstp) into `out` (element IJ = 0 of level 1, N planes)
+int wvl_launch(const ShimState& S, int nstp, double* out, int sink, double coef, double cm1);
+// N zeroed planes in the layout and alignment of one slot of u; *base is the allocation to free
+double* wvl_alloc_like_u(const Dev& d, hipStream_t s, double** base);
+// w of the current state into the library's work array (allocated on first use); nullptr and *rc < 0 on error
+const double* wvl_compute(const ShimState& S, int nstp, int* rc);
+void wvl_free();             // roms_gpu_finalize, roms_gpu_avg_begin(0)
 // Z-level slices (k_zslice.hip): ndep planes per sliced field in the 2-D
 // device layout, zero outside cells 1..Lm x 1..Mm, for rst_io.hip's writer.
 struct ZslView {

@@ -147,6 +147,9 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_avg_state.argtypes = [P(ctypes.c_int), P(ctypes.c_double), P(ctypes.c_int)]
     L.roms_gpu_avg_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
     L.roms_gpu_time_calc_avg.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_wvlcty.argtypes = [P(Tlev)]
+    L.roms_gpu_wvlcty_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_time_wvlcty.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     L.roms_gpu_zslice_begin.argtypes = [ctypes.c_int, ctypes.c_int, P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int),
                                         ctypes.c_int]
     L.roms_gpu_calc_zslice.argtypes = [P(Tlev)]
@@ -229,13 +232,13 @@ def halo_map(Lm, Mm, np_xi, np_eta, inode, jnode, ew_periodic, ns_periodic, dire
 
 HALO_DIRS = ("W", "E", "S", "N", "SW", "SE", "NW", "NE")
 # ROMS_WRT_* of include/roms_gpu.h (ocean_vars.opt wrt_* switches)
-WRT = dict(Z=1, Ub=2, Vb=4, U=8, V=16, T=32, R=64, O=128, Akv=256, Akt=512, Aks=1024, Hbls=2048, Hbbl=4096)
+WRT = dict(Z=1, Ub=2, Vb=4, U=8, V=16, T=32, R=64, O=128, Akv=256, Akt=512, Aks=1024, Hbls=2048, Hbbl=4096, W=8192)
 WRT_DEFAULT = 63
-WRT_ALL = 8191
+WRT_ALL = 16383
 # Model.avg names -> (ROMS_WRT_* bit, levels: 0 one plane, 1 N, 2 N+1)
 AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=(32, 1), temp=(32, 1), salt=(32, 1),
                   rho=(64, 1), omega=(128, 2), Akv=(256, 2), Akt=(512, 2), Aks=(1024, 2), hbls=(2048, 0),
-                  hbbl=(4096, 0))
+                  hbbl=(4096, 0), w=(8192, 1))
 # ROMS_ZSL_* of include/roms_gpu.h (zslice_output.opt wrt_*_zsl switches)
 ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
 ZSL_MAXDEP = 32
@@ -766,6 +769,21 @@ class Model:
         for _ in range(n):
             self._r("step")
             self.calc_avg(self.time(dt))
+
+    # ---- true vertical velocity (wvlcty.F) ----
+    def wvlcty(self):
+        """w at rho points [m/s] of the current state (FlxU, FlxV, u, v(nstp), z_r) as an (N, Mm+4, Lm+4)
+        array like get(); cells outside wvlcty_tile's range and its edge copies hold 0."""
+        self._chk(self.L.roms_gpu_wvlcty(ctypes.byref(self.t)), "wvlcty")
+        a = np.empty(self.N * self.shape2[0] * self.shape2[1], dtype=np.float64)
+        self._chk(self.L.roms_gpu_wvlcty_copy_out(a.ctypes.data, a.size), "wvlcty_copy_out")
+        return a.reshape((self.N,) + self.shape2)
+
+    def time_wvlcty(self, n):
+        """(ms of n store launches, ms of n running-mean launches; the latter 0 unless W is armed)."""
+        ms = (ctypes.c_double * 2)()
+        self._chk(self.L.roms_gpu_time_wvlcty(n, ctypes.byref(self.t), ms), "time_wvlcty")
+        return ms[0], ms[1]
 
     # ---- z-level slices (calc_zslice / wrt_zslice, zslice_output.F) ----
     def zslice_begin(self, depths, what=ZSL_U | ZSL_V, tracers=(1, 2), avg=False):
