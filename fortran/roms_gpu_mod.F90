@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 29 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 30 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
   integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
                                ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
@@ -68,6 +68,9 @@ module roms_gpu_mod
   integer(c_int), parameter :: ROMS_EXT_ZETA = 1, ROMS_EXT_UBAR = 2, ROMS_EXT_VBAR = 4, ROMS_EXT_U = 8, &
                                ROMS_EXT_V = 16, ROMS_EXT_TEMP = 32, ROMS_EXT_SALT = 64, ROMS_EXT_UP = 128, &
                                ROMS_EXT_VP = 256, ROMS_EXT_W = 512, ROMS_EXT_BGC = 1024
+  ! tracer budget terms of roms_gpu_tdiag_copy_out (ROMS_TDIA_*, diagnostics.F:83-88; SNAP: the pre-vertical Hz*t)
+  integer(c_int), parameter :: ROMS_TDIA_ADVX = 1, ROMS_TDIA_ADVY = 2, ROMS_TDIA_ADVZ = 3, ROMS_TDIA_MIXX = 4, &
+                               ROMS_TDIA_MIXY = 5, ROMS_TDIA_MIXZ = 6, ROMS_TDIA_SNAP = 7
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -329,6 +332,39 @@ module roms_gpu_mod
       integer(c_int), value :: n
       type(roms_tlev), intent(in) :: t
       real(c_double), intent(out) :: ms(2)
+    end function
+    ! tracer budget terms (k_tdiag.hip): DIAGNOSTICS with diag_trc, diagnostics.F
+    integer(c_int) function roms_gpu_tdiag_begin(ntd, itrc, do_avg) bind(c)
+      import :: c_int
+      integer(c_int), value :: ntd, do_avg
+      integer(c_int), intent(in) :: itrc(*)
+    end function
+    integer(c_int) function roms_gpu_tdiag_sample(on) bind(c)
+      import :: c_int
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function roms_gpu_tdiag_state(ntd, do_avg, navg, sampling) bind(c)
+      import :: c_int
+      integer(c_int), intent(out) :: ntd, do_avg, navg, sampling
+    end function
+    integer(c_int) function roms_gpu_tdiag_copy_out(itrc, term, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: itrc, term
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_wrt_tdiag(path, rec, total_rec, time, period, t) bind(c)
+      import :: c_int, c_double, c_char, roms_tlev
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: time, period
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_time_tdiag(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(inout) :: t
+      real(c_double), intent(out) :: ms(3)
     end function
     ! z-level slices (k_zslice.hip): calc_zslice / wrt_zslice of zslice_output.F
     integer(c_int) function roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg) bind(c)

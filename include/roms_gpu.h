@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 29
+#define ROMS_GPU_ABI_VERSION 30
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -638,6 +638,69 @@ int roms_gpu_time_calc_avg(int n, const roms_tlev *t, double *ms);
 int roms_gpu_wvlcty(const roms_tlev *t);
 int roms_gpu_wvlcty_copy_out(double *dst, long count);
 int roms_gpu_time_wvlcty(int n, const roms_tlev *t, double *ms);
+/* ---- tracer budget terms on the device (ABI 30): DIAGNOSTICS with diag_trc,
+ * diagnostics.F and its hooks in step3d_t_ISO.F, the non-isoneutral build.
+ * For every armed tracer six terms of the corrector step3d_t, each N planes in
+ * the layout of a rho field, C m^3/s, 0 outside the ranges named:
+ *  ADVX (i = 1..Lm+1, j = 1..Mm): the centred fourth-order flux of t(nrhs)
+ *    through the u face (diagnostics.F:620-639), grd(i) = (t(i)-t(i-1))*
+ *    umask(i), g2(i) = grd(i+1)+grd(i), advx = 0.5*(t(i)+t(i-1) -
+ *    0.1666666666666667*(g2(i)-g2(i-1)))*FlxU(i).  ADVY (i = 1..Lm, j =
+ *    1..Mm+1) alike in eta (:640-659).  On a physical, non-periodic edge of the
+ *    whole grid the difference one face outside is a copy of the first one
+ *    inside (compute_horiz_tracer_fluxes.h:50-84, 131-165); on a periodic side
+ *    or a rank boundary nothing is copied, so a decomposed run is bitwise the
+ *    single domain.
+ *  MIXX = FX - ADVX, MIXY = FE - ADVY (step3d_t_ISO.F:236-248): FX, FE the
+ *    UPSTREAM_TS fluxes the corrector applied, river faces overridden.
+ *  ADVZ (k = 1..N, i = 1..Lm, j = 1..Mm): the corrector's spline flux FC(k),
+ *    FC(N) = 0 (step3d_t_ISO.F:911-913).
+ *  MIXZ = ZFlx - ADVZ (step3d_t_ISO.F:914, 1104-1132): with S the content of
+ *    t(nnew) after the horizontal and before the vertical update, D(k) =
+ *    (S(k) - Hz(k)*t_new(k))/dt, ZFlx(1) = D(1)/(pm*pn), ZFlx(k) =
+ *    D(k)/(pm*pn) + ZFlx(k-1); t_new as the implicit solve leaves it, ahead of
+ *    t3dbc, the exchange and t3dmix.
+ * SNAP is S itself, kept for budget closure.
+ * tdiag_begin arms ntd tracers (1-based indices itrc[0..ntd-1]) and allocates
+ * seven zeroed arrays per tracer: the six terms (with do_avg their running
+ * means instead) and S; ntd = 0 disarms and frees.  It refuses (-1)
+ * adv_isoneutral (that branch defines other terms), an index outside 1..NT or
+ * repeated; a refused call leaves an earlier arming as it was.  Sampling is
+ * on after it; tdiag_sample switches it (the reference's
+ * calc_diag).  While armed and sampling every corrector -- the step3d_t entry
+ * and the one inside a whole step -- forms the terms: with do_avg navg += 1,
+ * coef = 1/navg, X_avg = X_avg*(1-coef) + X*coef (calc_diag_avg,
+ * diagnostics.F:709-732) in the lanes that form X, without the old mean's load
+ * at coef == 1.  Not armed, or not sampling, the corrector launches and
+ * allocates nothing more.  tdiag_state: a query (any pointer may be NULL).
+ * tdiag_copy_out: term ROMS_TDIA_* of armed tracer itrc as (N, Mm+4, Lm+4) in
+ * the host layout; the mean with do_avg, else the last sample; count must be
+ * that size; -1 for a tracer that is not armed.
+ * wrt_tdiag writes record rec (rec 1 creates the file) through the writer of
+ * the history files: ocean_time, time_step, per armed tracer <name>_advx,
+ * _advy, _advz, _mixx, _mixy, _mixz on (time, s_rho, eta_rho, xi_rho) with the
+ * reference's long names and units (create_diagvars, diagnostics.F:891-921),
+ * the global attribute diagnostic_options and, with do_avg, diag_avg_time =
+ * '<period, one decimal> seconds'.  With do_avg it then sets navg = 0.  With no
+ * sample since tdiag_begin (or, with do_avg, since the last record) it returns
+ * -4 and writes nothing.
+ * time_tdiag: n launches of each kernel over the whole interior for every
+ * armed tracer between two events, total milliseconds: ms[0] the snapshot,
+ * ms[1] the horizontal terms, ms[2] the vertical terms (with do_avg the mean
+ * sink at coef = 1/2: re-arm before the means are used).                      */
+#define ROMS_TDIA_ADVX 1
+#define ROMS_TDIA_ADVY 2
+#define ROMS_TDIA_ADVZ 3
+#define ROMS_TDIA_MIXX 4
+#define ROMS_TDIA_MIXY 5
+#define ROMS_TDIA_MIXZ 6
+#define ROMS_TDIA_SNAP 7
+int roms_gpu_tdiag_begin(int ntd, const int *itrc, int do_avg);
+int roms_gpu_tdiag_sample(int on);
+int roms_gpu_tdiag_state(int *ntd, int *do_avg, int *navg, int *sampling);
+int roms_gpu_tdiag_copy_out(int itrc, int term, double *dst, long count);
+int roms_gpu_wrt_tdiag(const char *path, int rec, int total_rec, double time, double period, const roms_tlev *t);
+int roms_gpu_time_tdiag(int n, roms_tlev *t, double ms[3]);
 /* ---- z-level slices on the device (ABI 26): calc_zslice / sigma_to_z /
  * calc_average / wrt_zslice of zslice_output.F.  u, v and chosen tracers, slot
  * t->nnew (the slot roms_gpu_wrt_his samples), interpolated from the model

@@ -816,6 +816,10 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
     launch_exchange_tracers(d, s, t.nnew);
     return;
   }
+  // tracer budget terms (k_tdiag.hip): armed and sampling, the horizontal terms now, from inputs the corrector
+  // leaves alone; the snapshot and the vertical terms inside run()
+  const bool td = tdiag_sampling();
+  if (td) tdiag_corrector(d, s, R, t);
   // horizontal fluxes, then the column solves, on a sub-range of the interior
   auto h_tiles = [&](const Range& r) {
     const dim3 gh = grid3_of(r, b.N), bh(kBX, kBY);
@@ -838,6 +842,7 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
     } else {
       h_tiles(r);
     }
+    if (td) tdiag_snap(d, s, r, t);
     dim3 gt = gridc_of(r);
     gt.z = b.NT;
     if (d.p.colseg) {
@@ -855,6 +860,7 @@ void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange) 
       hipLaunchKernelGGL(k_step3d_t_v<ColGlb>, gt, dim3(kCX), 0, s, d, r, t.nnew, t.nrhs);
     else
       hipLaunchKernelGGL(k_step3d_t_v<ColLds>, gt, dim3(kCX), col_lds_bytes(2, b.N), s, d, r, t.nnew, t.nrhs);
+    if (td) tdiag_vert(d, s, r, t);
   };
   auto edges = [&] {
     for (int itrc = 1; itrc <= b.NT; itrc++) launch_t3dbc(d, s, t, itrc);

@@ -557,6 +557,14 @@ void launch_step3d_uv2(const Dev& d, hipStream_t s, const Tlev& t);
 // own exchange of t(nnew) follows; the closed-wall ghosts are still set here)
 void launch_step3d_t(const Dev& d, hipStream_t s, const Tlev& t, bool exchange = true);
 void launch_t3dmix(const Dev& d, hipStream_t s, const Tlev& t);
+// Tracer budget terms (k_tdiag.hip; DIAGNOSTICS with diag_trc): launch_step3d_t's hooks while armed and sampling
+// (tdiag_sampling, a host flag of the calling thread).  tdiag_corrector, once per corrector ahead of its kernels:
+// the sample count and the horizontal terms over the whole interior R (inputs the corrector does not change);
+// tdiag_snap(r) between run(r)'s horizontal update and its column solve; tdiag_vert(r) after the solve
+bool tdiag_sampling();
+void tdiag_corrector(const Dev& d, hipStream_t s, const Range& R, const Tlev& t);
+void tdiag_snap(const Dev& d, hipStream_t s, const Range& r, const Tlev& t);
+void tdiag_vert(const Dev& d, hipStream_t s, const Range& r, const Tlev& t);
 void launch_u3dbc(const Dev& d, hipStream_t s, const Tlev& t);
 // river_frc.F hooks (k_river.hip): ubar/vbar(knew) and DU/DV_avg1 at river
 // faces after each fast step; u,v(nnew) at river faces (pred: predictor ranges)

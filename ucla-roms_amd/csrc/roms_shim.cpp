@@ -424,6 +424,7 @@ void free_all() {
   io_free();
   avg_free();
   wvl_free();
+  tdiag_free();
   zslice_free();
   extract_free();
   frc_free();
@@ -1546,7 +1547,8 @@ int roms_gpu_step(roms_tlev* t) {
   const bool first = (t->iic == t->forw_start);
   const bool store_huv = g.hzuv_env || g.hzuv_ext || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
   g.hzuv_valid = store_huv;
-  if (!g.use_graphs || first) {
+  // while the tracer budget terms are sampled the corrector's extra launches carry the step's own 1/navg: no replay
+  if (!g.use_graphs || first || tdiag_sampling()) {
     enqueue_step(t, rho_current, store_huv);
     return post_launch();
   }

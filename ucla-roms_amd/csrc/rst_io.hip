@@ -302,15 +302,44 @@ std::vector<OutVar> zslice_vars(const ShimState& S, const ZslView& zv) {
   return v;
 }
 
+// the variable list of a diagnostics record (create_diagvars, diagnostics.F:891-921; wrt_diag_trc :964-991): per
+// armed tracer <name>_advx, _advy, _advz, _mixx, _mixy, _mixz, N levels at rho points
+std::vector<OutVar> tdiag_vars(const ShimState& S, const TdiaView& tv) {
+  const Bounds& b = S.d->b;
+  const Part p = part_of(*S.dims);
+  static const char* sfx[6] = {"_advx", "_advy", "_advz", "_mixx", "_mixy", "_mixz"};
+  static const char* lnm[6] = {"x-advective flux", "y-advective flux", "z-advective flux", "mixing x-flux", "mixing y-flux",
+                               "mixing z-flux"};
+  std::vector<std::string> nm, un, ln;
+  tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
+  std::vector<OutVar> v;
+  for (size_t q = 0; q < tv.trc.size(); q++)
+    for (int a = 0; a < 6; a++) {
+      OutVar o;
+      o.name = nm[tv.trc[q] - 1] + sfx[a]; o.lname = lnm[a]; o.units = "C m^3/s"; o.grid = 'r'; o.levels = b.N;
+      o.slab = slab_of(b, p, tv.term[a][q], 'r', b.N, b.n2);
+      v.push_back(o);
+    }
+  return v;
+}
+
 void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst, bool avg = false,
-                 double period = 0.0, const ZslView* zv = nullptr) {
+                 double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr) {
   const Part p = part_of(*S.dims);
   const int N = S.d->b.N;
   // create_file (roms_read_write.F:1161-1208): ocean_time first, then the global attributes
   const int dtm = f.add_dim("time", 0);
   f.add_var("ocean_time", nc::NC_DOUBLE, {dtm},
             {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
-  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : "ROMS history file");
+  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : tv ? "ROMS diagnostics file" : "ROMS history file");
+  if (tv) {   // create_diagnostics_file (diagnostics.F:1006-1010); diag_avg_time as F12.1, left-adjusted (:754-755)
+    f.gatts.push_back(nc::Att::str("diagnostic_options", "Chosen Diagnostics = , Tracers"));
+    if (tv->do_avg) {
+      char tb[64];
+      snprintf(tb, sizeof tb, "%.1f seconds", period);
+      f.gatts.push_back(nc::Att::str("diag_avg_time", tb));
+    }
+  }
   if (avg) {   // the window length as F12.1, left-adjusted (basic_output.F:451-455, 705)
     char tb[64];
     snprintf(tb, sizeof tb, "%.1f seconds", period);
@@ -341,7 +370,7 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
 }
 
 int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask,
-                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr) {
+                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
@@ -356,12 +385,12 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   }
   if ((r = io_join(*S.err))) return r;
   const double* wvl = nullptr;
-  if (!rst && !avg && !zv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
+  if (!rst && !avg && !zv && !tv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
     if (t->nstp < 1 || t->nstp > 3) { *S.err = "roms_gpu_wrt_his: bad time levels"; return -1; }
     wvl = wvl_compute(S, t->nstp, &r);
     if (r) return r;
   }
-  std::vector<OutVar> vars = zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av, wvl);
+  std::vector<OutVar> vars = tv ? tdiag_vars(S, *tv) : zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av, wvl);
   size_t n = 0;
   for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
   if (!io.drain) {
@@ -404,9 +433,10 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   const roms_tlev tl = *t;
   const bool create = rec == 1;
   nc::File* proto = new nc::File();
-  if (create) define_file(*proto, S, vars, rst, avg, period, zv);
+  if (create) define_file(*proto, S, vars, rst, avg, period, zv, tv);
   const std::vector<double> depths = zv && create ? zv->vecdep : std::vector<double>();
   if (avg) avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
+  if (tv) tdiag_window_written();   // diagnostics.F:778
   io.job.status = 0;
   io.job.err.clear();
   io.job.running = true;
@@ -446,6 +476,11 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
 
 int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv) {
   return write_record(path, rec, total_rec, time, t, false, 0, false, 0.0, &zv);
+}
+
+int tdiag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
+                const TdiaView& tv) {
+  return write_record(path, rec, total_rec, time, t, false, 0, false, period, nullptr, &tv);
 }
 
 int io_writer_join(std::string& err) { return io_join(err); }

@@ -79,6 +79,21 @@ double* wvl_alloc_like_u(const Dev& d, hipStream_t s, double** base);
 // w of the current state into the library's work array (allocated on first use); nullptr and *rc < 0 on error
 const double* wvl_compute(const ShimState& S, int nstp, int* rc);
 void wvl_free();             // roms_gpu_finalize, roms_gpu_avg_begin(0)
+// Tracer budget terms (k_tdiag.hip): per armed tracer the six terms' device arrays (the means when do_avg), N planes
+// each in a rho field's layout, [ROMS_TDIA_* - 1], for rst_io.hip's writer
+struct TdiaView {
+  std::vector<int> trc;                  // tracer index (1..NT) of each armed tracer
+  bool do_avg = false;
+  int navg = 0;                          // samples in the open window (do_avg)
+  bool have = false;                     // there is a sample to write
+  std::vector<const double*> term[6];    // one per armed tracer
+};
+const TdiaView& tdiag_view();
+void tdiag_window_written();   // wrt_tdiag with do_avg: navg = 0
+void tdiag_free();             // roms_gpu_finalize
+// rst_io.hip: record rec of a diagnostics file (create_diagnostics_file, wrt_diag_trc) through the writer thread
+int tdiag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
+                const TdiaView& tv);
 // Z-level slices (k_zslice.hip): ndep planes per sliced field in the 2-D
 // device layout, zero outside cells 1..Lm x 1..Mm, for rst_io.hip's writer.
 struct ZslView {

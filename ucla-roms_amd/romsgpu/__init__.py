@@ -150,6 +150,13 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_wvlcty.argtypes = [P(Tlev)]
     L.roms_gpu_wvlcty_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_long]
     L.roms_gpu_time_wvlcty.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_tdiag_begin.argtypes = [ctypes.c_int, P(ctypes.c_int), ctypes.c_int]
+    L.roms_gpu_tdiag_sample.argtypes = [ctypes.c_int]
+    L.roms_gpu_tdiag_state.argtypes = [P(ctypes.c_int)] * 4
+    L.roms_gpu_tdiag_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_wrt_tdiag.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                     P(Tlev)]
+    L.roms_gpu_time_tdiag.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     L.roms_gpu_zslice_begin.argtypes = [ctypes.c_int, ctypes.c_int, P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int),
                                         ctypes.c_int]
     L.roms_gpu_calc_zslice.argtypes = [P(Tlev)]
@@ -242,6 +249,8 @@ AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=
 # ROMS_ZSL_* of include/roms_gpu.h (zslice_output.opt wrt_*_zsl switches)
 ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
 ZSL_MAXDEP = 32
+# ROMS_TDIA_* of include/roms_gpu.h (diagnostics.F:83-88; snap: the pre-vertical Hz*t, for budget closure)
+TDIA = dict(advx=1, advy=2, advz=3, mixx=4, mixy=5, mixz=6, snap=7)
 # ROMS_EXT_* of include/roms_gpu.h (the output_vars of an extraction object); up, vp, w, bgc are reported, not produced
 EXT = dict(zeta=1, ubar=2, vbar=4, u=8, v=16, temp=32, salt=64, up=128, vp=256, w=512, bgc=1024)
 EXT_3D = ("u", "v", "temp", "salt")
@@ -784,6 +793,44 @@ class Model:
         ms = (ctypes.c_double * 2)()
         self._chk(self.L.roms_gpu_time_wvlcty(n, ctypes.byref(self.t), ms), "time_wvlcty")
         return ms[0], ms[1]
+
+    # ---- tracer budget terms (DIAGNOSTICS with diag_trc, diagnostics.F) ----
+    def tdiag_begin(self, tracers, avg=False):
+        """Arm the six budget terms of the corrector for the 1-based tracer indices `tracers` (empty: disarm and
+        free); avg: running means, one sample per corrector.  Sampling is on afterwards."""
+        tr = np.ascontiguousarray(tracers, dtype=np.int32).ravel()
+        self._chk(self.L.roms_gpu_tdiag_begin(tr.size, tr.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), int(avg)),
+                  "tdiag_begin")
+
+    def tdiag_sample(self, on=True):
+        """The reference's calc_diag: whether the next correctors form (and average) the terms."""
+        self._chk(self.L.roms_gpu_tdiag_sample(int(on)), "tdiag_sample")
+
+    def tdiag_state(self):
+        """(ntd, avg, navg, sampling)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._chk(self.L.roms_gpu_tdiag_state(*[ctypes.byref(x) for x in v]), "tdiag_state")
+        return v[0].value, bool(v[1].value), v[2].value, bool(v[3].value)
+
+    def tdiag(self, itrc, term):
+        """Term `term` (TDIA: "advx" .. "mixz", "snap") of armed tracer itrc (1-based) as an (N, Mm+4, Lm+4) array
+        like get(): the mean with avg, else the last sample; 0 outside the term's range."""
+        if term not in TDIA:
+            raise ValueError("tdiag: unknown term %s" % term)
+        a = np.empty(self.N * self.shape2[0] * self.shape2[1], dtype=np.float64)
+        self._chk(self.L.roms_gpu_tdiag_copy_out(itrc, TDIA[term], a.ctypes.data, a.size), "tdiag_copy_out " + term)
+        return a.reshape((self.N,) + self.shape2)
+
+    def wrt_tdiag(self, path, rec, total_rec, time, period=0.0):
+        """wrt_diag_trc: record rec of this rank's diagnostics file; with avg it starts a fresh window."""
+        self._chk(self.L.roms_gpu_wrt_tdiag(path.encode(), rec, total_rec, time, period, ctypes.byref(self.t)),
+                  "wrt_tdiag")
+
+    def time_tdiag(self, n):
+        """(ms of n snapshot launches, of n horizontal-term launches, of n vertical-term launches)."""
+        ms = (ctypes.c_double * 3)()
+        self._chk(self.L.roms_gpu_time_tdiag(n, ctypes.byref(self.t), ms), "time_tdiag")
+        return ms[0], ms[1], ms[2]
 
     # ---- z-level slices (calc_zslice / wrt_zslice, zslice_output.F) ----
     def zslice_begin(self, depths, what=ZSL_U | ZSL_V, tracers=(1, 2), avg=False):
