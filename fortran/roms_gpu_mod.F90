@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 30 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 31 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
   integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
                                ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
@@ -71,6 +71,10 @@ module roms_gpu_mod
   ! tracer budget terms of roms_gpu_tdiag_copy_out (ROMS_TDIA_*, diagnostics.F:83-88; SNAP: the pre-vertical Hz*t)
   integer(c_int), parameter :: ROMS_TDIA_ADVX = 1, ROMS_TDIA_ADVY = 2, ROMS_TDIA_ADVZ = 3, ROMS_TDIA_MIXX = 4, &
                                ROMS_TDIA_MIXY = 5, ROMS_TDIA_MIXZ = 6, ROMS_TDIA_SNAP = 7
+  ! momentum budget terms of roms_gpu_uvdiag_copy_out (ROMS_UVD_*, diagnostics.F:56-63; PREV: u, v(nnew) as step3d_uv1 got them)
+  integer(c_int), parameter :: ROMS_UVD_U = 0, ROMS_UVD_V = 1
+  integer(c_int), parameter :: ROMS_UVD_PGR = 1, ROMS_UVD_COR = 2, ROMS_UVD_ADV = 3, ROMS_UVD_DIS = 4, &
+                               ROMS_UVD_HMX = 5, ROMS_UVD_VMX = 6, ROMS_UVD_CPL = 7, ROMS_UVD_PREV = 8
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -365,6 +369,38 @@ module roms_gpu_mod
       integer(c_int), value :: n
       type(roms_tlev), intent(inout) :: t
       real(c_double), intent(out) :: ms(3)
+    end function
+    ! momentum budget terms (k_uvdiag.hip): DIAGNOSTICS with diag_uv, diagnostics.F
+    integer(c_int) function roms_gpu_uvdiag_begin(on, do_avg) bind(c)
+      import :: c_int
+      integer(c_int), value :: on, do_avg
+    end function
+    integer(c_int) function roms_gpu_uvdiag_sample(on) bind(c)
+      import :: c_int
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function roms_gpu_uvdiag_state(armed, do_avg, navg, sampling) bind(c)
+      import :: c_int
+      integer(c_int), intent(out) :: armed, do_avg, navg, sampling
+    end function
+    integer(c_int) function roms_gpu_uvdiag_copy_out(comp, term, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: comp, term
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_wrt_diag(path, rec, total_rec, time, period, t) bind(c)
+      import :: c_int, c_double, c_char, roms_tlev
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: time, period
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_time_uvdiag(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(inout) :: t
+      real(c_double), intent(out) :: ms(4)
     end function
     ! z-level slices (k_zslice.hip): calc_zslice / wrt_zslice of zslice_output.F
     integer(c_int) function roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg) bind(c)

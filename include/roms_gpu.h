@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 30
+#define ROMS_GPU_ABI_VERSION 31
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -701,6 +701,76 @@ int roms_gpu_tdiag_state(int *ntd, int *do_avg, int *navg, int *sampling);
 int roms_gpu_tdiag_copy_out(int itrc, int term, double *dst, long count);
 int roms_gpu_wrt_tdiag(const char *path, int rec, int total_rec, double time, double period, const roms_tlev *t);
 int roms_gpu_time_tdiag(int n, roms_tlev *t, double ms[3]);
+/* ---- momentum budget terms on the device (ABI 31): DIAGNOSTICS with diag_uv,
+ * diagnostics.F and its hooks in prsgrd.F, compute_horiz_rhs_uv_terms.h,
+ * step3d_uv1.F, visc3d_S.F and step3d_uv2.F, the IMPLICIT_BOTTOM_DRAG branch.
+ * Seven terms per component, m^2/s^2, each N planes in the layout of u (of v);
+ * the u terms at i = istrU..iend, j = jstr..jend, the v terms at i =
+ * istr..iend, j = jstrV..jend, 0 elsewhere.  With dxdyi_u = 0.25*(pn(i-1,j)+
+ * pn(i,j))*(pm(i-1,j)+pm(i,j)) and the v forms the mirror image in eta:
+ *  PGR  ru*dxdyi_u*umask, ru as the corrector's prsgrd leaves it
+ *  COR  0.5*(UFx(i,j)+UFx(i-1,j))*dxdyi_u, -0.5*(VFe(i,j)+VFe(i,j-1))*dxdyi_v:
+ *       the Coriolis and curvilinear products over u, v(nrhs); 0 with neither
+ *  ADV  the centred fourth-order advection of u, v(nrhs) by the corrector's
+ *       FlxU, FlxV, We+Wi (set_diags_u_4th_adv, set_diags_v_4th_adv); second
+ *       order at the first and last flux of a physical, non-periodic edge of
+ *       the whole grid and at k = 1, N-1; fourth order on periodic sides and
+ *       rank boundaries, so a decomposed run is bitwise the single domain
+ *       (the reference tests *_msg_exch: the same on a closed single rank)
+ *  DIS  ru*dxdyi_u*umask - PGR - COR - ADV, ru the final right-hand side
+ *  HMX  the stress divergence of visc3d over u, v(nstp); 0 without uv_vis2
+ *  VMX  (u(nnew) - u_prev)/dt - ru*dxdyi_u: u_prev the u(nnew) step3d_uv1 is
+ *       given, u(nnew) the Hz*u its implicit solve leaves
+ *  CPL  -DC0*umask*0.5*(Hz(i,j,k)+Hz(i-1,j,k))/dt, DC0 the mismatch against
+ *       DU_avg1 that step3d_uv2 removes, Hz the one step3d_uv2 sees
+ * PREV is u_prev itself, kept for budget closure.
+ * uvdiag_begin(on = 1) allocates 14 zeroed term arrays (with do_avg their
+ * running means instead) and 4 snapshots; on = 0 disarms and frees; a refused
+ * call leaves an earlier arming as it was.  Sampling is on after it;
+ * uvdiag_sample switches it (the reference's calc_diag).  While armed and
+ * sampling the corrector's routines -- the entries roms_gpu_prsgrd,
+ * _step3d_uv1, _visc3d, _step3d_uv2 and the ones inside a whole step -- form
+ * the terms: prsgrd with nrhs == 3 keeps ru, rv; step3d_uv1 opens a sample
+ * (with do_avg navg += 1, coef = 1/navg, X_avg = X_avg*(1-coef) + X*coef,
+ * calc_diag_avg) and forms PGR, COR, ADV, DIS, VMX; visc3d and step3d_uv2 add
+ * HMX and CPL to the open sample once each; further calls before the next
+ * step3d_uv1 leave the terms alone.  A sample is complete after step3d_uv2.
+ * A whole step then runs prsgrd without the fused momentum terms, keeps the
+ * predictor's u, v(nnew) stored and is enqueued rather than replayed: the
+ * model fields are bitwise those of the default.  Not armed, or not sampling,
+ * the routines launch and allocate nothing more.
+ * uvdiag_state: a query (any pointer may be NULL).  uvdiag_copy_out: term
+ * ROMS_UVD_* of component ROMS_UVD_U / ROMS_UVD_V as (N, Mm+4, Lm+4) in the
+ * host layout; the mean with do_avg, else the last sample.
+ * wrt_diag writes record rec (rec 1 creates the file) through the writer of
+ * the history files: ocean_time, time_step, u_pgr, u_cor, u_adv, u_dis, u_hmx,
+ * u_vmx, u_cpl on (time, s_rho, eta_rho, xi_u), v_* on (time, s_rho, eta_v,
+ * xi_rho) with the reference's long names and units (create_diagvars,
+ * diagnostics.F:812-889), then, if tracers are armed too (tdiag_begin), their
+ * variables; the global attribute diagnostic_options lists what is in the
+ * file and, with do_avg, diag_avg_time = '<period, one decimal> seconds'.
+ * With do_avg both windows restart after the record.  -4 with no complete
+ * sample; -1 if the two sets disagree on do_avg.
+ * time_uvdiag: n launches of each kernel over the whole interior between two
+ * events, total milliseconds: ms[0] the snapshots, ms[1] PGR..DIS and VMX,
+ * ms[2] HMX, ms[3] CPL (with do_avg the mean sink at coef = 1/2: re-arm before
+ * the means are used).                                                      */
+#define ROMS_UVD_U 0
+#define ROMS_UVD_V 1
+#define ROMS_UVD_PGR 1
+#define ROMS_UVD_COR 2
+#define ROMS_UVD_ADV 3
+#define ROMS_UVD_DIS 4
+#define ROMS_UVD_HMX 5
+#define ROMS_UVD_VMX 6
+#define ROMS_UVD_CPL 7
+#define ROMS_UVD_PREV 8
+int roms_gpu_uvdiag_begin(int on, int do_avg);
+int roms_gpu_uvdiag_sample(int on);
+int roms_gpu_uvdiag_state(int *armed, int *do_avg, int *navg, int *sampling);
+int roms_gpu_uvdiag_copy_out(int comp, int term, double *dst, long count);
+int roms_gpu_wrt_diag(const char *path, int rec, int total_rec, double time, double period, const roms_tlev *t);
+int roms_gpu_time_uvdiag(int n, roms_tlev *t, double ms[4]);
 /* ---- z-level slices on the device (ABI 26): calc_zslice / sigma_to_z /
  * calc_average / wrt_zslice of zslice_output.F.  u, v and chosen tracers, slot
  * t->nnew (the slot roms_gpu_wrt_his samples), interpolated from the model

@@ -417,6 +417,8 @@ void launch_prsgrd(const Dev& d, hipStream_t s, const Tlev& t, int uv_up, bool p
     tiles(R2);
   }
   ktimer_mark(s, kTimedPrsgrdUv, 1, 1);
+  // momentum budget terms (k_uvdiag.hip): ru, rv as the corrector's prsgrd leaves them (prsgrd.F:458-465)
+  if (uvdiag_sampling() && t.nrhs == 3 && uv_up < 0) uvdiag_prsgrd(d, s);
 }
 // k_prsgrd_uv<true> adds the horizontal momentum r.h.s. of k_uv_horiz1 on
 // the same inputs: usable when the caller runs uv_horiz next with nothing

@@ -156,7 +156,9 @@ __global__ void __launch_bounds__(64) k_uv1(Dev d, Range R, int nnew, int nrhs) 
 // chain through the waves in k order (wave s adds its levels to wave s-1's
 // running sum, handed over in LDS between barriers): the reference's
 // operations in its order, bit-identical.
-template <bool kLds>
+// kRu (the momentum budget terms, k_uvdiag.hip): the final ru(k) is stored where it is formed, for the rows the
+// lane owns, as uv1_col does; the default instantiation stores nothing more.
+template <bool kLds, bool kRu = false>
 __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_seg(Dev d, Range R, int nnew, int nrhs) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
   __shared__ SegXchg X;
@@ -210,6 +212,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_seg(Dev d, Rang
     const int k = c0 + p;
     const long o = cell(k);
     const double r = k == 1 ? rr[o] - fl[1] : rr[o] - fl[p + 1 < KR ? p + 1 : KR - 1] + fl[p];
+    if constexpr (kRu) {
+      if (act && p < n) const_cast<double*>(rr)[o] = r;
+    }
     if constexpr (kLds) {
       rk[p] = r;
     } else {
@@ -314,8 +319,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_seg(Dev d, Rang
 // k_pre_uv_segb<false>, did not store u(nnew) = Hz*u(nstp); each row's base is
 // formed here from the row's Hz pair in LDS and u(nstp), with the predictor's
 // expression and operand order (the same bits: Hz changes only in the fast
-// loop that follows).  One load per row either way. ----
-template <bool kForm>
+// loop that follows).  One load per row either way.
+// kRu: as k_uv1_seg's. ----
+template <bool kForm, bool kRu = false>
 __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Range R, int nnew, int nrhs, int nstp) {
   const uint3 bI = seg_tile(d.p.seg_order, d.p.seg_xg);
   __shared__ SegXchg X;
@@ -357,6 +363,9 @@ __global__ void __launch_bounds__(kSegBlock * kSegJMax, 2) k_uv1_segb(Dev d, Ran
     const int k = c0 + p;
     const double rro = LD(rr, vo, lev(k));
     rk[p] = k == 1 ? rro - fl[1] : rro - fl[p + 1 < KR ? p + 1 : KR - 1] + fl[p];
+    if constexpr (kRu) {
+      if (p < n) rr.st(rk[p], act ? vo + lev(k) : kBufOff, 0u);
+    }
   }
   int tl = tid;
   __asm__ volatile("" : "+v"(tl));
@@ -434,10 +443,22 @@ void setup_uv1_seg() {
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
   (void)hipFuncSetAttribute((const void*)k_uv1_segb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
+  // the instantiations that store the final ru (k_uvdiag.hip)
+  (void)hipFuncSetAttribute((const void*)k_uv1_seg<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)((size_t)kSegRows * kSegMaxS * kSegCW * kSegJMax * sizeof(double)));
+  (void)hipFuncSetAttribute((const void*)k_uv1_seg<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
+  (void)hipFuncSetAttribute((const void*)k_uv1_segb<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)uv1_seg_lds_bytes(kSegBlock * kSegJMax));
 }
 
 void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done, bool lean_uv) {
   const Bounds& b = d.b;
+  // momentum budget terms (k_uvdiag.hip): armed and sampling, a sample opens with u, v(nnew) as they come in, the
+  // segment solvers store the final ru, rv as the column form does, and the terms follow the solve.  The caller
+  // has left the predictor's u, v(nnew) stored (no lean_uv) and the corrector's prsgrd unfused
+  const bool ud = uvdiag_sampling() && !lean_uv;
+  if (ud) uvdiag_uv1_begin(d, s, t);
   if (!uv_done) launch_uv_horiz(d, s, t.nrhs, 1);
   Range R{b.istr, b.iend, b.jstr, b.jend};
   dim3 g = gridc_of(R);
@@ -445,7 +466,16 @@ void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
   if (d.p.colseg) {
     const dim3 gs = seg_uv_grid(d, R, d.p.seg_jrows), bs(kCX, seg_waves(b.N), d.p.seg_jrows);
     ktimer_mark(s, kTimedUv1Seg, 0);
-    if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf && lean_uv)   // the predictor left u(nnew) unstored: nstp = 3 - nnew
+    if (ud && d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf)
+      hipLaunchKernelGGL((k_uv1_segb<false, true>), gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew,
+                         t.nrhs, t.nstp);
+    else if (ud && d.p.uv1_lds && d.p.uv_adv)
+      hipLaunchKernelGGL((k_uv1_seg<true, true>), gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew,
+                         t.nrhs);
+    else if (ud)
+      hipLaunchKernelGGL((k_uv1_seg<false, true>), gs, bs, (size_t)b.N * kSegCW * d.p.seg_jrows * sizeof(double), s, d,
+                         R, t.nnew, t.nrhs);
+    else if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf && lean_uv)   // the predictor left u(nnew) unstored: nstp = 3 - nnew
       hipLaunchKernelGGL(k_uv1_segb<true>, gs, bs, uv1_seg_lds_bytes(bs.x * bs.y * bs.z), s, d, R, t.nnew, t.nrhs,
                          t.nstp);
     else if (d.p.uv1_lds && d.p.uv_adv && d.p.seg_buf)
@@ -462,6 +492,7 @@ void launch_step3d_uv1(const Dev& d, hipStream_t s, const Tlev& t, bool uv_done,
     hipLaunchKernelGGL(k_uv1<ColGlb>, g, dim3(kCX), 0, s, d, R, t.nnew, t.nrhs);
   else
     hipLaunchKernelGGL(k_uv1<ColLds>, g, dim3(kCX), col_lds_bytes(2, b.N), s, d, R, t.nnew, t.nrhs);
+  if (ud) uvdiag_uv1_end(d, s, t);
 }
 
 // ---- visc3d: harmonic viscosity along S; adds dt*cff to u,v(indx) (Hz*u)
@@ -831,6 +862,7 @@ __global__ void __launch_bounds__(256, 3) k_visc3d_stg(Dev d, Range R, int nstp)
 void launch_visc3d(const Dev& d, hipStream_t s, const Tlev& t) {
   const Bounds& b = d.b;
   Range R{b.istr, b.iend, b.jstr, b.jend};
+  if (uvdiag_sampling()) uvdiag_visc3d(d, s, t);   // hmx from u, v(nstp) and Hz, which visc3d leaves alone
   if (d.p.visc_stg && (d.p.vg & (kVg2Visc << kVg2Shift)))
     hipLaunchKernelGGL(k_visc3d_stg<true>, grid_of(R), dim3(kBX, kBY), 0, s, d, R, t.nstp);
   else if (d.p.visc_stg)
@@ -1245,6 +1277,7 @@ void launch_step3d_uv2(const Dev& d, hipStream_t s, const Tlev& t) {
   const int j0 = b.ns_periodic ? b.jstr : b.jstrR, j1 = b.ns_periodic ? b.jend : b.jendR;
   Range R2{iv0 < iu0 ? iv0 : iu0, iu1 > iv1 ? iu1 : iv1, j0, j1};
   const int kl = (b.N + 3) / 4;
+  if (uvdiag_sampling()) uvdiag_uv2(d, s, t);   // cpl from u, v(nnew) as they come in
   if (!d.p.obc && d.p.uv2_fused && kl <= 25) {
     dim3 gf = chain_grid_of(R1);
     gf.z = d.p.chain_dirz ? 2 : 1;

@@ -565,6 +565,17 @@ bool tdiag_sampling();
 void tdiag_corrector(const Dev& d, hipStream_t s, const Range& R, const Tlev& t);
 void tdiag_snap(const Dev& d, hipStream_t s, const Range& r, const Tlev& t);
 void tdiag_vert(const Dev& d, hipStream_t s, const Range& r, const Tlev& t);
+// Momentum budget terms (k_uvdiag.hip; DIAGNOSTICS with diag_uv): the hooks of launch_prsgrd, launch_step3d_uv1,
+// launch_visc3d and launch_step3d_uv2 while armed and sampling (uvdiag_sampling, a host flag of the calling thread).
+// uvdiag_prsgrd: after the corrector's unfused prsgrd, ru_pgr = ru*dxdyi_u*umask; uvdiag_uv1_begin opens a sample
+// (navg, coef) and keeps u, v(nnew); uvdiag_uv1_end forms pgr, cor, adv, dis, vmx from the final ru the solvers
+// stored; uvdiag_visc3d and uvdiag_uv2 add hmx and cpl to the open sample, once each
+bool uvdiag_sampling();
+void uvdiag_prsgrd(const Dev& d, hipStream_t s);
+void uvdiag_uv1_begin(const Dev& d, hipStream_t s, const Tlev& t);
+void uvdiag_uv1_end(const Dev& d, hipStream_t s, const Tlev& t);
+void uvdiag_visc3d(const Dev& d, hipStream_t s, const Tlev& t);
+void uvdiag_uv2(const Dev& d, hipStream_t s, const Tlev& t);
 void launch_u3dbc(const Dev& d, hipStream_t s, const Tlev& t);
 // river_frc.F hooks (k_river.hip): ubar/vbar(knew) and DU/DV_avg1 at river
 // faces after each fast step; u,v(nnew) at river faces (pred: predictor ranges)

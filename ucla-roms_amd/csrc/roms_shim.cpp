@@ -425,6 +425,7 @@ void free_all() {
   avg_free();
   wvl_free();
   tdiag_free();
+  uvdiag_free();
   zslice_free();
   extract_free();
   frc_free();
@@ -591,7 +592,11 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   // u, v(nnew = 3), the OBC forms read nstp and nrhs besides, omega, rho_eos,
   // lmd_vmix and prsgrd read u, v(nrhs = 3) at most, and the output samplers
   // run between steps; Hz changes only in the fast loop after step3d_uv1
-  const bool lean_uv = lean_uv_step(d, T);
+  // while the momentum budget terms are sampled (k_uvdiag.hip) the corrector takes two alternatives that are
+  // bitwise the default: u, v(indx) stored (u_prev is read from it) and prsgrd unfused (ru, rv after prsgrd alone)
+  const bool uvd = uvdiag_sampling();
+  const bool lean_uv = lean_uv_step(d, T) && !uvd;
+  const bool fuse_corr = fuse_uv && !uvd;
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 0 : -1, p_ready));
   XJOIN_T(2, xt);   // pre_step3d reads We, Akv, Akt across the halo
   TIMED(ROMS_R_PRE_STEP3D, DEFER(launch_pre_step3d(d, s, T, fuse_uv, hb_done, lean_uv)));   // t(nnew)
@@ -617,9 +622,9 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   launch_bulk_flux(d, s, T.nrhs);   // set_forces (main.F:433): BULK_FRC only
   if (g.cfg.lmd_mixing) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs, lean_akt))); akt_lmd_done(); }   // Akv, Akt, hbls, hbbl
   frc_step_phase(d, s, 3, pot);     // set_bry_all 'forward' + set_tides (main.F:438-441)
-  TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_uv ? 1 : -1, p_ready));
+  TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_corr ? 1 : -1, p_ready));
   XJOIN_T(16, xt);   // step3d_uv1 reads We and Akv across the halo
-  TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_uv, lean_uv));
+  TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_corr, lean_uv));
   if (g.cfg.uv_vis2) TIMED(ROMS_R_VISC3D, launch_visc3d(d, s, T));
   // the fast loop is timed as one interval over its nfast steps (kernel-level
   // count, as the graph replays it: no event between two fast steps)
@@ -1548,7 +1553,7 @@ int roms_gpu_step(roms_tlev* t) {
   const bool store_huv = g.hzuv_env || g.hzuv_ext || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
   g.hzuv_valid = store_huv;
   // while the tracer budget terms are sampled the corrector's extra launches carry the step's own 1/navg: no replay
-  if (!g.use_graphs || first || tdiag_sampling()) {
+  if (!g.use_graphs || first || tdiag_sampling() || uvdiag_sampling()) {
     enqueue_step(t, rho_current, store_huv);
     return post_launch();
   }

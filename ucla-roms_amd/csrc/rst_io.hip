@@ -323,18 +323,41 @@ std::vector<OutVar> tdiag_vars(const ShimState& S, const TdiaView& tv) {
   return v;
 }
 
+// the momentum variables of a diagnostics record (create_diagvars, diagnostics.F:812-889; wrt_diag_uv :923-962):
+// u_pgr .. u_cpl at u points, v_pgr .. v_cpl at v points, N levels
+std::vector<OutVar> uvdiag_vars(const ShimState& S, const UvdView& uv) {
+  const Bounds& b = S.d->b;
+  const Part p = part_of(*S.dims);
+  static const char* sfx[7] = {"_pgr", "_cor", "_adv", "_dis", "_hmx", "_vmx", "_cpl"};
+  static const char* lnm[7] = {"Hydrostatic Presssure Gradient", "Coriolis and Curvilinear", "Advection (Hor. and Vert.",
+                               "Numerical dissipation", "Horizontal mixing", "Vertical mixing", "2D/3D coupling"};
+  std::vector<OutVar> v;
+  for (int c = 0; c < 2; c++)
+    for (int a = 0; a < 7; a++) {
+      OutVar o;
+      o.name = std::string(c == 0 ? "u" : "v") + sfx[a]; o.lname = lnm[a]; o.units = "m^2/s^2";
+      o.grid = c == 0 ? 'u' : 'v'; o.levels = b.N;
+      o.slab = slab_of(b, p, uv.term[c][a], o.grid, b.N, b.n2);
+      v.push_back(o);
+    }
+  return v;
+}
+
 void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst, bool avg = false,
-                 double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr) {
+                 double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr,
+                 const UvdView* uv = nullptr) {
   const Part p = part_of(*S.dims);
   const int N = S.d->b.N;
   // create_file (roms_read_write.F:1161-1208): ocean_time first, then the global attributes
   const int dtm = f.add_dim("time", 0);
   f.add_var("ocean_time", nc::NC_DOUBLE, {dtm},
             {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
-  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : tv ? "ROMS diagnostics file" : "ROMS history file");
-  if (tv) {   // create_diagnostics_file (diagnostics.F:1006-1010); diag_avg_time as F12.1, left-adjusted (:754-755)
-    f.gatts.push_back(nc::Att::str("diagnostic_options", "Chosen Diagnostics = , Tracers"));
-    if (tv->do_avg) {
+  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : (tv || uv) ? "ROMS diagnostics file" : "ROMS history file");
+  if (tv || uv) {   // create_diagnostics_file (diagnostics.F:1006-1010); diag_avg_time as F12.1, left-adjusted (:754-755)
+    // init_diagnostics (:231-234): what is in the file
+    f.gatts.push_back(nc::Att::str("diagnostic_options", std::string("Chosen Diagnostics = ") + (uv ? "Momentum" : "") +
+                                                             (tv ? ", Tracers" : "")));
+    if (uv ? uv->do_avg : tv->do_avg) {
       char tb[64];
       snprintf(tb, sizeof tb, "%.1f seconds", period);
       f.gatts.push_back(nc::Att::str("diag_avg_time", tb));
@@ -370,7 +393,8 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
 }
 
 int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask,
-                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr) {
+                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr,
+                 const UvdView* uv = nullptr) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
@@ -385,12 +409,17 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   }
   if ((r = io_join(*S.err))) return r;
   const double* wvl = nullptr;
-  if (!rst && !avg && !zv && !tv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
+  if (!rst && !avg && !zv && !tv && !uv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
     if (t->nstp < 1 || t->nstp > 3) { *S.err = "roms_gpu_wrt_his: bad time levels"; return -1; }
     wvl = wvl_compute(S, t->nstp, &r);
     if (r) return r;
   }
-  std::vector<OutVar> vars = tv ? tdiag_vars(S, *tv) : zv ? zslice_vars(S, *zv) : record_vars(S, *t, rst, mask, av, wvl);
+  std::vector<OutVar> vars = uv ? uvdiag_vars(S, *uv) : tv ? tdiag_vars(S, *tv) : zv ? zslice_vars(S, *zv)
+                                                                                   : record_vars(S, *t, rst, mask, av, wvl);
+  if (uv && tv) {   // create_diagvars' order: the momentum variables, then the tracers'
+    const std::vector<OutVar> tvars = tdiag_vars(S, *tv);
+    vars.insert(vars.end(), tvars.begin(), tvars.end());
+  }
   size_t n = 0;
   for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
   if (!io.drain) {
@@ -433,10 +462,11 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   const roms_tlev tl = *t;
   const bool create = rec == 1;
   nc::File* proto = new nc::File();
-  if (create) define_file(*proto, S, vars, rst, avg, period, zv, tv);
+  if (create) define_file(*proto, S, vars, rst, avg, period, zv, tv, uv);
   const std::vector<double> depths = zv && create ? zv->vecdep : std::vector<double>();
   if (avg) avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
   if (tv) tdiag_window_written();   // diagnostics.F:778
+  if (uv) uvdiag_window_written();
   io.job.status = 0;
   io.job.err.clear();
   io.job.running = true;
@@ -481,6 +511,11 @@ int zslice_write(const char* path, int rec, int total_rec, double time, const ro
 int tdiag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
                 const TdiaView& tv) {
   return write_record(path, rec, total_rec, time, t, false, 0, false, period, nullptr, &tv);
+}
+
+int diag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
+               const UvdView& uv, const TdiaView* tv) {
+  return write_record(path, rec, total_rec, time, t, false, 0, false, period, nullptr, tv, &uv);
 }
 
 int io_writer_join(std::string& err) { return io_join(err); }

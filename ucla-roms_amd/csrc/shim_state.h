@@ -94,6 +94,21 @@ void tdiag_free();             // roms_gpu_finalize
 // rst_io.hip: record rec of a diagnostics file (create_diagnostics_file, wrt_diag_trc) through the writer thread
 int tdiag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
                 const TdiaView& tv);
+// Momentum budget terms (k_uvdiag.hip): the seven terms' device arrays of u and of v (the means when do_avg), N
+// planes each in the layout of u (of v), [comp][ROMS_UVD_* - 1], for rst_io.hip's writer
+struct UvdView {
+  bool armed = false, do_avg = false;
+  int navg = 0;                          // samples in the open window (do_avg)
+  bool have = false;                     // there is a complete sample to write
+  const double* term[2][7] = {};
+};
+const UvdView& uvdiag_view();
+void uvdiag_window_written();   // wrt_diag with do_avg: navg = 0
+void uvdiag_free();             // roms_gpu_finalize
+// rst_io.hip: record rec of a diagnostics file with the momentum terms and, tv given, the armed tracers' terms
+// (create_diagvars, wrt_diag_uv, wrt_diag_trc) through the writer thread
+int diag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
+               const UvdView& uv, const TdiaView* tv);
 // Z-level slices (k_zslice.hip): ndep planes per sliced field in the 2-D
 // device layout, zero outside cells 1..Lm x 1..Mm, for rst_io.hip's writer.
 struct ZslView {

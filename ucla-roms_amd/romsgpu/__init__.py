@@ -157,6 +157,13 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_wrt_tdiag.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                      P(Tlev)]
     L.roms_gpu_time_tdiag.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_uvdiag_begin.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.roms_gpu_uvdiag_sample.argtypes = [ctypes.c_int]
+    L.roms_gpu_uvdiag_state.argtypes = [P(ctypes.c_int)] * 4
+    L.roms_gpu_uvdiag_copy_out.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_wrt_diag.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                    P(Tlev)]
+    L.roms_gpu_time_uvdiag.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     L.roms_gpu_zslice_begin.argtypes = [ctypes.c_int, ctypes.c_int, P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int),
                                         ctypes.c_int]
     L.roms_gpu_calc_zslice.argtypes = [P(Tlev)]
@@ -251,6 +258,9 @@ ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
 ZSL_MAXDEP = 32
 # ROMS_TDIA_* of include/roms_gpu.h (diagnostics.F:83-88; snap: the pre-vertical Hz*t, for budget closure)
 TDIA = dict(advx=1, advy=2, advz=3, mixx=4, mixy=5, mixz=6, snap=7)
+# ROMS_UVD_* of include/roms_gpu.h (diagnostics.F:56-63; prev: u, v(nnew) as step3d_uv1 got them, for budget closure)
+UVD = dict(pgr=1, cor=2, adv=3, dis=4, hmx=5, vmx=6, cpl=7, prev=8)
+UVD_COMP = dict(u=0, v=1)
 # ROMS_EXT_* of include/roms_gpu.h (the output_vars of an extraction object); up, vp, w, bgc are reported, not produced
 EXT = dict(zeta=1, ubar=2, vbar=4, u=8, v=16, temp=32, salt=64, up=128, vp=256, w=512, bgc=1024)
 EXT_3D = ("u", "v", "temp", "salt")
@@ -831,6 +841,44 @@ class Model:
         ms = (ctypes.c_double * 3)()
         self._chk(self.L.roms_gpu_time_tdiag(n, ctypes.byref(self.t), ms), "time_tdiag")
         return ms[0], ms[1], ms[2]
+
+    # ---- momentum budget terms (DIAGNOSTICS with diag_uv, diagnostics.F) ----
+    def uvdiag_begin(self, avg=False, on=True):
+        """Arm the seven budget terms of u and of v (on=False: disarm and free); avg: running means, one sample per
+        corrector.  Sampling is on afterwards."""
+        self._chk(self.L.roms_gpu_uvdiag_begin(int(on), int(avg)), "uvdiag_begin")
+
+    def uvdiag_sample(self, on=True):
+        """The reference's calc_diag: whether the next correctors form (and average) the terms."""
+        self._chk(self.L.roms_gpu_uvdiag_sample(int(on)), "uvdiag_sample")
+
+    def uvdiag_state(self):
+        """(armed, avg, navg, sampling)."""
+        v = [ctypes.c_int() for _ in range(4)]
+        self._chk(self.L.roms_gpu_uvdiag_state(*[ctypes.byref(x) for x in v]), "uvdiag_state")
+        return bool(v[0].value), bool(v[1].value), v[2].value, bool(v[3].value)
+
+    def uvdiag(self, comp, term):
+        """Term `term` (UVD: "pgr" .. "cpl", "prev") of component "u" or "v" as an (N, Mm+4, Lm+4) array like get():
+        the mean with avg, else the last sample; 0 outside the component's range."""
+        if term not in UVD or comp not in UVD_COMP:
+            raise ValueError("uvdiag: unknown component or term %s %s" % (comp, term))
+        a = np.empty(self.N * self.shape2[0] * self.shape2[1], dtype=np.float64)
+        self._chk(self.L.roms_gpu_uvdiag_copy_out(UVD_COMP[comp], UVD[term], a.ctypes.data, a.size),
+                  "uvdiag_copy_out " + term)
+        return a.reshape((self.N,) + self.shape2)
+
+    def wrt_diag(self, path, rec, total_rec, time, period=0.0):
+        """do_diagnostics' record of this rank's diagnostics file: the momentum terms and, if tracers are armed too,
+        theirs; with avg it starts fresh windows."""
+        self._chk(self.L.roms_gpu_wrt_diag(path.encode(), rec, total_rec, time, period, ctypes.byref(self.t)),
+                  "wrt_diag")
+
+    def time_uvdiag(self, n):
+        """(ms of n launches of the snapshots, of k_uvdiag_rhs, of k_uvdiag_hmx, of k_uvdiag_cpl)."""
+        ms = (ctypes.c_double * 4)()
+        self._chk(self.L.roms_gpu_time_uvdiag(n, ctypes.byref(self.t), ms), "time_uvdiag")
+        return tuple(ms)
 
     # ---- z-level slices (calc_zslice / wrt_zslice, zslice_output.F) ----
     def zslice_begin(self, depths, what=ZSL_U | ZSL_V, tracers=(1, 2), avg=False):
