@@ -236,7 +236,9 @@ def test_coast_run_open_edges(size, name):
 
 @pytest.mark.parametrize("name", list(coasts.COASTS))
 def test_coast_run_curvgrid(name):
-    """The same at 121 x 12 on non-uniform metrics (curvgrid = 1): the masked
+    """The same at 121 x 12 on the analytic curvgrid = 1 grid, whose metrics
+    are separable (pm = pm(j), pn = pn(i), f constant; grids that vary along
+    both axes: tests/test_gpu_metrics.py): the masked
     curvature terms of k_common.h:683-721 beside land, and, prsgrd taking no
     strips on such a grid (asserted), k_prsgrd_uv's tiles with the mask of
     the clamped entry point (k_prsgrd.hip:180-202) in every row."""

@@ -9,7 +9,10 @@ switch variants.
       of Examples/Iceland/Iceland_parent/cppdefs.opt -- OBC_M2FLATHER /
       M3ORLANSKI / TORLANSKI with *_FRC_BRY data, SPONGE, MASKING (island),
       CURVGRID, NONLIN+SPLIT EOS, LMD_MIXING+KPP+BKPP+RIMIX+NONLOCAL without
-      LMD_CONVEC -- dt = 900 s, ndtfast = 30 (nfast 41, .../roms.in).
+      LMD_CONVEC -- dt = 900 s, ndtfast = 30 (nfast 41, .../roms.in).  The
+      analytic CURVGRID grid is separable (pm = pm(j), pn = pn(i), f constant),
+      unlike Iceland's; tests/test_gpu_metrics.py runs this switch set on
+      metrics that vary along both axes.
       Single domain vs the oracle; 4x2 processor grid (8 subdomains, one
       thread each) vs the single domain bitwise.  The 4x2 check runs without
       the sponge: the reference sets the sponge bands on each rank's own

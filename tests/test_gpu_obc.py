@@ -105,7 +105,8 @@ def test_open_boundary_routine_parity(routine, obc):
 @pytest.mark.parametrize("routine", ["pre_step3d", "step3d_uv1"])
 def test_curvgrid_momentum_rhs_parity(routine):
     """CURVGRID curvature terms in the momentum r.h.s. (compute_horiz_rhs_uv_terms.h:4-12)
-    on non-uniform metrics; ru/rv carry them into u,v(nnew)."""
+    on the analytic curvgrid = 1 grid, whose metrics are separable (pm = pm(j), pn = pn(i), f constant;
+    tests/test_gpu_metrics.py runs grids that vary along both axes); ru/rv carry them into u,v(nnew)."""
     cfg = obc_cfg(curv=1)
     o, m = make_pair(cfg)
     assert float(np.max(np.abs(o.field("dndx")))) > 0.0 and float(np.max(np.abs(o.field("dmde")))) > 0.0

@@ -179,6 +179,20 @@ def test_curvgrid():
     assert np.ptp(E["pm"][0][2:13, 5]) > 0 and np.ptp(E["pn"][0][5, 2:38]) > 0
 
 
+def test_rough_metrics():
+    """pm and pn vary along both axes (tests/metrics.py `rough`, every entry different from its neighbours): a term
+    that reads pm or pn one cell off differs from the restatement."""
+    import metrics
+    cfg = small_basin()
+    o = oracle.Oracle(cfg)
+    o.init()
+    metrics.apply_grid(o, None, metrics.rough(cfg.LLm, cfg.MMm))
+    o.step(3)
+    _, E = run_case(cfg, o=o)
+    for n in ("pm", "pn"):
+        assert metrics.neighbours_differ(E[n][0], (-1, cfg.MMm + 2, -1, cfg.LLm + 2)) == 0, n
+
+
 def test_surface_and_nonlocal_terms_reach_mixz():
     got, _ = run_case(small_basin(lmd=oracle.LMD_ALL, surf_flux=1))
     plain, _ = run_case(small_basin())

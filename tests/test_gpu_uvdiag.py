@@ -126,6 +126,24 @@ def test_curvgrid():
     assert np.ptp(s["pm"][2:13, 5]) > 0 and np.abs(s["dndx"]).max() > 0
 
 
+def test_rough_metrics():
+    """pm, pn and f vary along both axes (tests/metrics.py `rough`, every entry different from its neighbours), with
+    the curvature terms on: a term that reads a metric one cell off, or dm_p for dm_v, differs from the restatement."""
+    import metrics
+    from test_uvdiag_ref import VISC2
+    cfg = small_basin(curvgrid=1)
+    o = oracle.Oracle(cfg)
+    o.init()
+    o.field("visc2_r")[...] = VISC2
+    o.field("visc2_p")[...] = VISC2
+    metrics.apply_grid(o, None, metrics.rough(cfg.LLm, cfg.MMm))
+    o.step(3)
+    _, s = run_case(cfg, o=o)
+    R = metrics.ranges(cfg.LLm, cfg.MMm)
+    for n in ("fomn", "dndx", "dmde", "dm_r", "dn_r", "dm_p", "dn_p", "dn_u", "dm_v"):
+        assert metrics.neighbours_differ(s[n], R[n]) == 0, n
+
+
 def test_open_boundaries():
     cfg = obc_cfg(obc=15, island=0, LLm=36, MMm=11, N=5, sizex=72e3, sizey=22e3)
     run_case(cfg, model=obc_model)

@@ -70,6 +70,31 @@ def test_kernel_equals_the_restatement(name):
         assert (x["rmask"][2:M + 2, 2:L + 2] == 0).any()
 
 
+def test_rough_metrics():
+    """pm and pn vary along both axes (tests/metrics.py `rough`, put into the model after init): a pm or pn read one
+    cell off, or one for the other, differs from the restatement, which the reference's routine pins on random planes."""
+    import metrics
+    import oracle
+    from test_gpu_parity import basin_cfg
+    case = dict(BASIN_LMD, curvgrid=True)
+    cfg = basin_cfg(nonlin=True, LLm=case["LLm"], MMm=case["MMm"], N=case["N"], sizex=case["sizex"], sizey=case["sizey"])
+    cfg.lmd, cfg.surf_flux, cfg.curvgrid = oracle.LMD_ALL, 1, 1
+    o = oracle.Oracle(cfg)
+    o.init()
+    m = romsgpu.Model.from_case(**case)
+    try:
+        planes = metrics.apply_grid(o, m, metrics.rough(cfg.LLm, cfg.MMm))
+        m.step(3)
+        w = m.wvlcty()
+        ref = wvlcty_ref.of_model(m, False)
+        for n in ("pm", "pn"):
+            assert np.array_equal(m.get(n)[0], planes[n])
+            assert metrics.neighbours_differ(planes[n], (-1, cfg.MMm + 2, -1, cfg.LLm + 2)) == 0, n
+    finally:
+        m.close()
+    assert np.array_equal(w, ref) and np.abs(w).max() > 0
+
+
 @pytest.mark.parametrize("N", [3, 4, 5])
 def test_level_counts_of_the_rolling_window(N):
     """The one-sided ends with one (N = 3), two (4) and three (5) levels of the four-point middle loop
