@@ -115,7 +115,9 @@ struct AvgBuf {
 };
 
 struct AvgCtx {
-  AvgView v;                       // what rst_io.hip's writer sees
+  AvgView v;                       // what rst_io.hip's averages record reads
+  MeanWindow w;                    // w.avg is set while armed
+  double t_avg = 0.0;              // the mean time of the window's samples
   std::vector<AvgBuf> bufs;
   std::vector<AvgField> fields;    // host copy of the table
   AvgField* d_tab = nullptr;
@@ -150,20 +152,22 @@ unsigned avg_blocks(long nmax) {
   return (unsigned)(b < 1 ? 1 : b > kAvgBlocks ? kAvgBlocks : b);
 }
 
-int avg_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) {
+// one sample of the window A.w has just opened
+int avg_launch(const ShimState& S, const roms_tlev& t) {
+  const double coef = A.w.coef, cm1 = A.w.cm1;
   const Bounds& b = S.d->b;
   const long ok = (long)(t.knew - 1) * b.n2, on = (long)(t.nstp - 1) * b.n3;
   const dim3 grid(avg_blocks(A.nmax), (unsigned)(A.fields.empty() ? 1 : A.fields.size()));
   // AKs samples Akt(isalt), which whole steps may leave unformed (shim_akt_sync)
   if ((A.v.mask & ROMS_WRT_AKS) && shim_akt_sync() != hipSuccess) return -3;
   if (!A.fields.empty()) {
-    if (coef == 1.0) hipLaunchKernelGGL(k_calc_avg<true>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
+    if (A.w.sink() == kMeanFirst) hipLaunchKernelGGL(k_calc_avg<true>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
     else hipLaunchKernelGGL(k_calc_avg<false>, grid, dim3(256), 0, S.s, A.d_tab, ok, on, coef, cm1);
     if (hipGetLastError() != hipSuccess) return -3;
   }
   // w (wvlcty.F) is a launch of its own: k_wvlcty with the running mean as its sink, over the cells it
   // computes or copies (k_wvlcty.hip)
-  if (A.v.wvl) return wvl_launch(S, t.nstp, A.v.wvl, coef == 1.0 ? kWvlMeanFirst : kWvlMean, coef, cm1);
+  if (A.v.wvl) return wvl_launch(S, t.nstp, A.v.wvl, A.w.sink(), coef, cm1);
   return 0;
 }
 
@@ -172,7 +176,11 @@ bool tlev_ok(const roms_tlev* t) { return t && t->knew >= 1 && t->knew <= 4 && t
 }  // namespace
 
 const AvgView& avg_view() { return A.v; }
-void avg_window_written() { A.v.navg = 0; }
+const MeanWindow& avg_window(double* t_avg) {
+  *t_avg = A.t_avg;
+  return A.w;
+}
+void avg_window_written() { A.w.written(); }
 void avg_free() { avg_release(); }
 
 }  // namespace roms
@@ -246,8 +254,7 @@ int roms_gpu_avg_begin(int wrt_mask) {
     return -2;
   }
   V.mask = mask;
-  V.navg = 0;
-  V.t_avg = 0.0;
+  A.w.avg = true;
   return 0;
 }
 
@@ -257,10 +264,10 @@ int roms_gpu_calc_avg(const roms_tlev* t, double time) {
   if (r) return r;
   if (!A.v.mask) { *S.err = "roms_gpu_calc_avg: averaging is not armed (roms_gpu_avg_begin)"; return -4; }
   if (!tlev_ok(t)) { *S.err = "roms_gpu_calc_avg: bad time levels"; return -1; }
-  const double coef = 1.0 / (double)(A.v.navg + 1), cm1 = 1.0 - coef;
-  if ((r = avg_launch(S, *t, coef, cm1))) { *S.err = "roms_gpu_calc_avg: launch failed"; return r; }
-  A.v.navg += 1;
-  A.v.t_avg = A.v.t_avg * cm1 + time * coef;
+  const MeanWindow before = A.w;
+  A.w.open();
+  if ((r = avg_launch(S, *t))) { A.w = before; *S.err = "roms_gpu_calc_avg: launch failed"; return r; }
+  A.t_avg = A.t_avg * A.w.cm1 + time * A.w.coef;
   return 0;
 }
 
@@ -268,8 +275,8 @@ int roms_gpu_avg_state(int* navg, double* t_avg, int* mask) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  if (navg) *navg = A.v.navg;
-  if (t_avg) *t_avg = A.v.t_avg;
+  if (navg) *navg = A.w.reported();
+  if (t_avg) *t_avg = A.t_avg;
   if (mask) *mask = A.v.mask;
   return 0;
 }
@@ -318,21 +325,12 @@ int roms_gpu_time_calc_avg(int n, const roms_tlev* t, double* ms) {
   if (r) return r;
   if (!A.v.mask) { *S.err = "roms_gpu_time_calc_avg: averaging is not armed (roms_gpu_avg_begin)"; return -4; }
   if (!tlev_ok(t) || n < 1 || !ms) { *S.err = "roms_gpu_time_calc_avg: bad arguments"; return -1; }
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { *S.err = "roms_gpu_time_calc_avg: events"; return -2; }
-  (void)hipEventRecord(e0, S.s);
-  for (int q = 0; q < n && !r; q++) {
-    const double coef = 1.0 / (double)(A.v.navg + 1);
-    r = avg_launch(S, *t, coef, 1.0 - coef);
-    A.v.navg += 1;
-  }
-  (void)hipEventRecord(e1, S.s);
-  float f = 0.f;
-  if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&f, e0, e1) != hipSuccess) r = r ? r : -2;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (r) { *S.err = "roms_gpu_time_calc_avg: launch or timing failed"; return r; }
-  *ms = (double)f;
+  const double f = time_rounds(S.s, n, false, [&]() {
+    A.w.open();
+    return avg_launch(S, *t);
+  });
+  if (f < 0) { *S.err = "roms_gpu_time_calc_avg: launch or timing failed"; return (int)f; }
+  *ms = f;
   return 0;
 }
 

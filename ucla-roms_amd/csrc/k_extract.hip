@@ -947,7 +947,7 @@ int roms_gpu_extract_copy_out(int iobj, int var_bit, double* dst, long count) {
 }
 
 // n launches of the interpolation, then n of the remap, each between two
-// events on the library stream: ms[0], ms[1] their totals (tools/extract_cost.py)
+// events of its own on the library stream: ms[0], ms[1] their totals (tools/extract_cost.py)
 int roms_gpu_time_calc_extract(int n, const roms_tlev* t, double* ms) {
   ShimState S;
   int r = shim_enter(S, true);
@@ -955,23 +955,13 @@ int roms_gpu_time_calc_extract(int n, const roms_tlev* t, double* ms) {
   if (n < 1 || !ms) { *S.err = "roms_gpu_time_calc_extract: bad arguments"; return -1; }
   if ((r = ext_prepare(S, t, "roms_gpu_time_calc_extract"))) return r;
   if ((r = ext_sample(S))) { *S.err = "roms_gpu_time_calc_extract: launch failed"; return r; }
-  hipEvent_t e[3];
-  for (int q = 0; q < 3; q++)
-    if (hipEventCreate(&e[q]) != hipSuccess) { *S.err = "roms_gpu_time_calc_extract: events"; return -2; }
   const bool remap = E.NP > 0 && E.mismatch && (ext_union() & kExt3d);
-  (void)hipEventRecord(e[0], S.s);
-  for (int q = 0; q < n && E.NP > 0; q++) ext_launch_interp(S);
-  (void)hipEventRecord(e[1], S.s);
-  for (int q = 0; q < n && remap; q++) ext_launch_remap(S);
-  (void)hipEventRecord(e[2], S.s);
-  float f0 = 0.f, f1 = 0.f;
-  if (hipEventSynchronize(e[2]) != hipSuccess || hipEventElapsedTime(&f0, e[0], e[1]) != hipSuccess ||
-      hipEventElapsedTime(&f1, e[1], e[2]) != hipSuccess || hipGetLastError() != hipSuccess)
-    r = -2;
-  for (int q = 0; q < 3; q++) (void)hipEventDestroy(e[q]);
-  if (r) { *S.err = "roms_gpu_time_calc_extract: launch or timing failed"; return r; }
-  ms[0] = (double)f0;
-  ms[1] = (double)f1;
+  ms[0] = time_rounds(S.s, n, false, [&]() { if (E.NP > 0) ext_launch_interp(S); return 0; });
+  ms[1] = ms[0] < 0 ? 0.0 : time_rounds(S.s, n, false, [&]() { if (remap) ext_launch_remap(S); return 0; });
+  if (ms[0] < 0 || ms[1] < 0) {
+    *S.err = "roms_gpu_time_calc_extract: launch or timing failed";
+    return (int)(ms[0] < 0 ? ms[0] : ms[1]);
+  }
   return 0;
 }
 

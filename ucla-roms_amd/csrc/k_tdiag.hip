@@ -48,14 +48,6 @@
 namespace roms {
 namespace {
 
-enum TdSink : int { kTdStore = 0, kTdMean = 1, kTdMeanFirst = 2 };
-template <int SINK>
-__device__ __forceinline__ void td_put(double* __restrict__ p, double x, double coef, double cm1) {
-  if (SINK == kTdStore) *p = x;
-  else if (SINK == kTdMeanFirst) *p = x * coef;
-  else *p = *p * cm1 + x * coef;
-}
-
 // Tn, snap: element IJ = 0 of level 1 of the tracer's t(nnew) slot / its snapshot
 __global__ void __launch_bounds__(256) k_tdiag_snap(Dev d, Range R, const double* __restrict__ Tn,
                                                     double* __restrict__ snap) {
@@ -108,8 +100,8 @@ __global__ void __launch_bounds__(256) k_tdiag_h(Dev d, Range R, int itrc, const
       if (rx) river_tracer_flux(d, 0, i, j, k, itrc, FX);
       const double g0 = el[2] + el[1], gm = el[1] + el[0];   // g2(i), g2(i-1)
       const double adv = 0.5 * (t0 + t1 - 0.1666666666666667 * (g0 - gm)) * Fl;
-      td_put<SINK>(advx + ij + kk, adv, coef, cm1);
-      td_put<SINK>(mixx + ij + kk, FX - adv, coef, cm1);
+      sink_put<SINK>(advx + ij + kk, adv, coef, cm1);
+      sink_put<SINK>(mixx + ij + kk, FX - adv, coef, cm1);
     }
     if (fe) {
       double el[3];
@@ -121,8 +113,8 @@ __global__ void __launch_bounds__(256) k_tdiag_h(Dev d, Range R, int itrc, const
       if (re) river_tracer_flux(d, 1, i, j, k, itrc, FE);
       const double g0 = el[2] + el[1], gm = el[1] + el[0];
       const double adv = 0.5 * (t0 + t1 - 0.1666666666666667 * (g0 - gm)) * Fl;
-      td_put<SINK>(advy + ij + kk, adv, coef, cm1);
-      td_put<SINK>(mixy + ij + kk, FE - adv, coef, cm1);
+      sink_put<SINK>(advy + ij + kk, adv, coef, cm1);
+      sink_put<SINK>(mixy + ij + kk, FE - adv, coef, cm1);
     }
   }
 }
@@ -151,8 +143,8 @@ __global__ void __launch_bounds__(64) k_tdiag_v(Dev d, Range R, const double* __
     const double D = (snap[ij + o] - Hz[o] * Tn[ij + o]) / dt;
     zf = k == 1 ? D / pmn : D / pmn + zf;
     const double adv = A[k];
-    td_put<SINK>(advz + ij + o, adv, coef, cm1);
-    td_put<SINK>(mixz + ij + o, zf - adv, coef, cm1);
+    sink_put<SINK>(advz + ij + o, adv, coef, cm1);
+    sink_put<SINK>(mixz + ij + o, zf - adv, coef, cm1);
   }
 }
 
@@ -164,11 +156,8 @@ struct TdTrc {
 };
 struct TdCtx {
   std::vector<TdTrc> trc;
-  bool avg = false, sampling = false;
-  bool have = false;        // a sample since begin (avg: since the last record)
-  int navg = 0;
-  double coef = 1.0, cm1 = 0.0;   // of the corrector under way
-  TdiaView view;
+  bool sampling = false;
+  MeanWindow w;   // w.have: a sample since begin (avg: since the last record); coef, cm1 of the corrector under way
 };
 thread_local TdCtx Td;
 
@@ -178,8 +167,6 @@ void td_release() {
       if (q) (void)hipFree(q);
   Td = TdCtx{};
 }
-
-int td_sink() { return !Td.avg ? kTdStore : (Td.coef == 1.0 ? kTdMeanFirst : kTdMean); }
 
 const double* slot_of(const Dev& d, int tlev, int itrc) {
   return d.f.t + (long)(tlev - 1) * d.b.n3 + (long)(itrc - 1) * 3 * d.b.n3;
@@ -199,9 +186,7 @@ void launch_h(const Dev& d, hipStream_t s, const Range& R, int nrhs, int sink, d
            *my = t.p[ROMS_TDIA_MIXY - 1];
     const double* Tr = slot_of(d, nrhs, t.itrc);
 #define ROMS_TD_H(SINK) hipLaunchKernelGGL((k_tdiag_h<SINK>), g, blk, 0, s, d, R, t.itrc, Tr, ax, ay, mx, my, coef, cm1)
-    if (sink == kTdStore) ROMS_TD_H(kTdStore);
-    else if (sink == kTdMeanFirst) ROMS_TD_H(kTdMeanFirst);
-    else ROMS_TD_H(kTdMean);
+    ROMS_SINKS(sink, ROMS_TD_H);
 #undef ROMS_TD_H
   }
 }
@@ -218,29 +203,17 @@ void launch_v(const Dev& d, hipStream_t s, const Range& r, int nnew, int nrhs, i
     else hipLaunchKernelGGL((k_tdiag_v<ColLds, SINK>), g, dim3(kCX), col_lds_bytes(2, d.b.N), s, d, r, Tr, Tn,    \
                             sn, az, mz, coef, cm1);                                                               \
   } while (0)
-    if (sink == kTdStore) ROMS_TD_V(kTdStore);
-    else if (sink == kTdMeanFirst) ROMS_TD_V(kTdMeanFirst);
-    else ROMS_TD_V(kTdMean);
+    ROMS_SINKS(sink, ROMS_TD_V);
 #undef ROMS_TD_V
   }
 }
 
 void set_lds_limit(int N) {
   const int bytes = (int)col_lds_bytes(2, N);
-  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kTdStore>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kTdMean>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kTdMeanFirst>, hipFuncAttributeMaxDynamicSharedMemorySize,
+  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kStore>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kMean>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  (void)hipFuncSetAttribute((const void*)k_tdiag_v<ColLds, kMeanFirst>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             bytes);
-}
-
-void fill_view() {
-  TdiaView& V = Td.view;
-  V = TdiaView{};
-  V.do_avg = Td.avg;
-  for (const TdTrc& t : Td.trc) {
-    V.trc.push_back(t.itrc);
-    for (int q = 0; q < 6; q++) V.term[q].push_back(t.p[q]);
-  }
 }
 
 }  // namespace
@@ -248,27 +221,30 @@ void fill_view() {
 bool tdiag_sampling() { return Td.sampling; }
 
 void tdiag_corrector(const Dev& d, hipStream_t s, const Range& R, const Tlev& t) {
-  Td.navg = Td.avg ? Td.navg + 1 : 1;
-  Td.coef = 1.0 / (double)Td.navg;
-  Td.cm1 = 1.0 - Td.coef;
-  Td.have = true;
-  launch_h(d, s, R, t.nrhs, td_sink(), Td.coef, Td.cm1);
+  Td.w.open();
+  launch_h(d, s, R, t.nrhs, Td.w.sink(), Td.w.coef, Td.w.cm1);
 }
 void tdiag_snap(const Dev& d, hipStream_t s, const Range& r, const Tlev& t) { launch_snap(d, s, r, t.nnew); }
 void tdiag_vert(const Dev& d, hipStream_t s, const Range& r, const Tlev& t) {
-  launch_v(d, s, r, t.nnew, t.nrhs, td_sink(), Td.coef, Td.cm1);
+  launch_v(d, s, r, t.nnew, t.nrhs, Td.w.sink(), Td.w.coef, Td.w.cm1);
 }
 
-const TdiaView& tdiag_view() {
-  Td.view.navg = Td.navg;
-  Td.view.have = Td.have;
-  return Td.view;
+// the variable list of a diagnostics record (create_diagvars, diagnostics.F:891-921; wrt_diag_trc :964-991): per
+// armed tracer <name>_advx, _advy, _advz, _mixx, _mixy, _mixz, N levels at rho points
+bool tdiag_record(const ShimState& S, std::vector<OutVar>& vars, bool* do_avg, bool* have) {
+  static const char* sfx[6] = {"_advx", "_advy", "_advz", "_mixx", "_mixy", "_mixz"};
+  static const char* lnm[6] = {"x-advective flux", "y-advective flux", "z-advective flux", "mixing x-flux", "mixing y-flux",
+                               "mixing z-flux"};
+  *do_avg = Td.w.avg;
+  *have = Td.w.have;
+  std::vector<std::string> nm, un, ln;
+  io_tracer_meta(S, nm, un, ln);
+  for (const TdTrc& t : Td.trc)
+    for (int a = 0; a < 6; a++)
+      vars.push_back(out_var(S, nm[t.itrc - 1] + sfx[a], lnm[a], "C m^3/s", 'r', S.d->b.N, 0, t.p[a], S.d->b.n2));
+  return !Td.trc.empty();
 }
-void tdiag_window_written() {
-  if (!Td.avg) return;
-  Td.navg = 0;
-  Td.have = false;
-}
+void tdiag_window_written() { Td.w.written(); }   // diagnostics.F:778
 void tdiag_free() { td_release(); }
 
 }  // namespace roms
@@ -313,9 +289,8 @@ int roms_gpu_tdiag_begin(int ntd, const int* itrc, int do_avg) {
     }
   }
   if (!S.d->f.colscr) set_lds_limit(b.N);
-  Td.avg = do_avg != 0;
+  Td.w.avg = do_avg != 0;
   Td.sampling = true;
-  fill_view();
   if (hipStreamSynchronize(S.s) != hipSuccess) { td_release(); *S.err = "roms_gpu_tdiag_begin: zero fill failed"; return -2; }
   return 0;
 }
@@ -334,8 +309,8 @@ int roms_gpu_tdiag_state(int* ntd, int* do_avg, int* navg, int* sampling) {
   int r = shim_enter(S, true);
   if (r) return r;
   if (ntd) *ntd = (int)Td.trc.size();
-  if (do_avg) *do_avg = Td.avg ? 1 : 0;
-  if (navg) *navg = Td.avg ? Td.navg : 0;
+  if (do_avg) *do_avg = Td.w.avg ? 1 : 0;
+  if (navg) *navg = Td.w.reported();
   if (sampling) *sampling = Td.sampling ? 1 : 0;
   return 0;
 }
@@ -361,8 +336,18 @@ int roms_gpu_wrt_tdiag(const char* path, int rec, int total_rec, double time, do
   int r = shim_enter(S, true);
   if (r) return r;
   if (Td.trc.empty()) { *S.err = "roms_gpu_wrt_tdiag: not armed (roms_gpu_tdiag_begin)"; return -4; }
-  if (!Td.have) { *S.err = "roms_gpu_wrt_tdiag: no sample to write (no corrector ran while sampling)"; return -4; }
-  return tdiag_write(path, rec, total_rec, time, period, t, tdiag_view());
+  if (!Td.w.have) { *S.err = "roms_gpu_wrt_tdiag: no sample to write (no corrector ran while sampling)"; return -4; }
+  RecordSpec spec;
+  bool avg, have;
+  (void)tdiag_record(S, spec.vars, &avg, &have);
+  spec.type = "ROMS diagnostics file";   // create_diagnostics_file (diagnostics.F:1006-1010)
+  // init_diagnostics (:231-234) names what is in the file: no momentum terms ahead of the comma here
+  spec.gatts.push_back({"diagnostic_options", "Chosen Diagnostics = , Tracers"});
+  if (avg) spec.gatts.push_back({"diag_avg_time", seconds_att(period)});   // :754-755
+  spec.time = time;
+  if ((r = write_record(S, path, rec, total_rec, t, spec))) return r;
+  tdiag_window_written();
+  return 0;
 }
 
 // n launches of each kernel over the whole interior, every armed tracer, between two events on the library stream
@@ -380,26 +365,16 @@ int roms_gpu_time_tdiag(int n, roms_tlev* t, double ms[3]) {
   const Dev& d = *S.d;
   const Bounds& b = d.b;
   const Range R{b.istr, b.iend, b.jstr, b.jend};
-  const int sink = Td.avg ? kTdMean : kTdStore;
-  hipEvent_t e[2];
-  if (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess) { *S.err = "roms_gpu_time_tdiag: events"; return -2; }
-  ms[0] = ms[1] = ms[2] = 0.0;
-  for (int which = 0; which < 3 && !r; which++) {
-    for (int q = -1; q < n; q++) {   // q = -1: an untimed first launch
-      if (q == 0) (void)hipEventRecord(e[0], S.s);
+  const int sink = Td.w.avg ? kMean : kStore;
+  for (int which = 0; which < 3; which++) {
+    ms[which] = time_rounds(S.s, n, true, [&]() {   // an untimed first launch
       if (which == 0) launch_snap(d, S.s, R, t->nnew);
       else if (which == 1) launch_h(d, S.s, R, t->nrhs, sink, 0.5, 0.5);
       else launch_v(d, S.s, R, t->nnew, t->nrhs, sink, 0.5, 0.5);
-    }
-    (void)hipEventRecord(e[1], S.s);
-    float f = 0.f;
-    if (hipEventSynchronize(e[1]) != hipSuccess || hipEventElapsedTime(&f, e[0], e[1]) != hipSuccess) r = -2;
-    if (hipGetLastError() != hipSuccess) r = -3;
-    ms[which] = (double)f;
+      return 0;
+    });
+    if (ms[which] < 0) { *S.err = "roms_gpu_time_tdiag: launch or timing failed"; return (int)ms[which]; }
   }
-  (void)hipEventDestroy(e[0]);
-  (void)hipEventDestroy(e[1]);
-  if (r) { *S.err = "roms_gpu_time_tdiag: launch or timing failed"; return r; }
   return 0;
 }
 

@@ -42,14 +42,6 @@
 namespace roms {
 namespace {
 
-enum UvSink : int { kUvStore = 0, kUvMean = 1, kUvMeanFirst = 2 };
-template <int SINK>
-__device__ __forceinline__ void uv_put(double* __restrict__ p, double x, double coef, double cm1) {
-  if (SINK == kUvStore) *p = x;
-  else if (SINK == kUvMeanFirst) *p = x * coef;
-  else *p = *p * cm1 + x * coef;
-}
-
 // the device arrays: [0..6] the u terms ROMS_UVD_PGR..CPL, [7..13] the v terms, then the four snapshots
 constexpr int kUvTerms = 7, kUvRuPgr = 14, kUvRvPgr = 15, kUvUPrev = 16, kUvVPrev = 17, kUvArr = 18;
 struct UvArrs {
@@ -150,11 +142,11 @@ __global__ void __launch_bounds__(256) k_uvdiag_rhs(Dev d, Range R, int nnew, in
       const double pg = A.p[kUvRuPgr][o], rf = F.ru[o];
       const double ds = rf * dxu * um - pg - cr - adv;
       const double vx = (Un[o] - A.p[kUvUPrev][o]) / dt - rf * dxu;
-      uv_put<SINK>(A.p[0] + o, pg, coef, cm1);
-      uv_put<SINK>(A.p[1] + o, cr, coef, cm1);
-      uv_put<SINK>(A.p[2] + o, adv, coef, cm1);
-      uv_put<SINK>(A.p[3] + o, ds, coef, cm1);
-      uv_put<SINK>(A.p[5] + o, vx, coef, cm1);
+      sink_put<SINK>(A.p[0] + o, pg, coef, cm1);
+      sink_put<SINK>(A.p[1] + o, cr, coef, cm1);
+      sink_put<SINK>(A.p[2] + o, adv, coef, cm1);
+      sink_put<SINK>(A.p[3] + o, ds, coef, cm1);
+      sink_put<SINK>(A.p[5] + o, vx, coef, cm1);
       ua = ub; ub = uc; uc = ud; ud = Ur[ij + lev(k + 3)];
     }
     if (dv) {
@@ -182,11 +174,11 @@ __global__ void __launch_bounds__(256) k_uvdiag_rhs(Dev d, Range R, int nnew, in
       const double pg = A.p[kUvRvPgr][o], rf = F.rv[o];
       const double ds = rf * dxv * vm - pg - cr - adv;
       const double vx = (Vn[o] - A.p[kUvVPrev][o]) / dt - rf * dxv;
-      uv_put<SINK>(A.p[7] + o, pg, coef, cm1);
-      uv_put<SINK>(A.p[8] + o, cr, coef, cm1);
-      uv_put<SINK>(A.p[9] + o, adv, coef, cm1);
-      uv_put<SINK>(A.p[10] + o, ds, coef, cm1);
-      uv_put<SINK>(A.p[12] + o, vx, coef, cm1);
+      sink_put<SINK>(A.p[7] + o, pg, coef, cm1);
+      sink_put<SINK>(A.p[8] + o, cr, coef, cm1);
+      sink_put<SINK>(A.p[9] + o, adv, coef, cm1);
+      sink_put<SINK>(A.p[10] + o, ds, coef, cm1);
+      sink_put<SINK>(A.p[12] + o, vx, coef, cm1);
       va = vb; vb = vc; vc = vd; vd = Vr[ij + lev(k + 3)];
     }
   }
@@ -240,7 +232,7 @@ __global__ void __launch_bounds__(256) k_uvdiag_hmx(Dev d, Range R, int nstp, Uv
     uvd_psi(d, ij + sj, kk, l, UFe1, t1);
     const double h = 0.5 * uv_dxdyi(F, ij, 1) *
                      ((pn[ij - 1] + pn[ij]) * (UFx0 - UFxm) + (pm[ij - 1] + pm[ij]) * (UFe1 - UFe0));
-    uv_put<SINK>(A.p[4] + o, h, coef, cm1);
+    sink_put<SINK>(A.p[4] + o, h, coef, cm1);
   }
   if (dv) {
     double VFx1, VFem;
@@ -248,7 +240,7 @@ __global__ void __launch_bounds__(256) k_uvdiag_hmx(Dev d, Range R, int nstp, Uv
     uvd_rho(d, ij - sj, kk, l, t1, VFem);
     const double h = 0.5 * uv_dxdyi(F, ij, sj) *
                      ((pn[ij - sj] + pn[ij]) * (VFx1 - VFx0) + (pm[ij - sj] + pm[ij]) * (VFe0 - VFem));
-    uv_put<SINK>(A.p[11] + o, h, coef, cm1);
+    sink_put<SINK>(A.p[11] + o, h, coef, cm1);
   }
 }
 
@@ -281,20 +273,18 @@ __global__ void __launch_bounds__(256) k_uvdiag_cpl(Dev d, Range R, int nnew, Uv
 #pragma unroll 4
   for (int k = 1; k <= N; k++) {
     o = (long)(k - 1) * n2;
-    uv_put<SINK>(out + o, -DC0 * msk * 0.5 * (Hz[o] + Hz[o - s]) / dt, coef, cm1);
+    sink_put<SINK>(out + o, -DC0 * msk * 0.5 * (Hz[o] + Hz[o - s]) / dt, coef, cm1);
   }
 }
 
 struct UvCtx {
   double* base[kUvArr] = {};
   UvArrs A = {};
-  bool armed = false, avg = false, sampling = false;
+  bool armed = false, sampling = false;
   bool open = false;        // step3d_uv1 opened a sample that step3d_uv2 has not closed
   bool hmx_done = false, cpl_done = false;
-  bool have = false;        // a complete sample since begin (avg: since the last record)
-  int navg = 0;
-  double coef = 1.0, cm1 = 0.0;   // of the open sample
-  UvdView view;
+  MeanWindow w;             // coef, cm1 of the open sample
+  bool have = false;        // a complete sample since begin (avg: since the last record); w.have is set a sample early
 };
 thread_local UvCtx Uv;
 
@@ -304,15 +294,7 @@ void uv_release() {
   Uv = UvCtx{};
 }
 
-int uv_sink() { return !Uv.avg ? kUvStore : (Uv.coef == 1.0 ? kUvMeanFirst : kUvMean); }
 Range uv_range(const Bounds& b) { return Range{b.istr, b.iend, b.jstr, b.jend}; }
-
-#define ROMS_UV_SINKS(sink, CALL)                 \
-  do {                                            \
-    if ((sink) == kUvStore) { CALL(kUvStore); }   \
-    else if ((sink) == kUvMeanFirst) { CALL(kUvMeanFirst); } \
-    else { CALL(kUvMean); }                       \
-  } while (0)
 
 void launch_snap_r(const Dev& d, hipStream_t s) {
   const Range R = uv_range(d.b);
@@ -326,31 +308,36 @@ void launch_rhs(const Dev& d, hipStream_t s, int nnew, int nrhs, int sink, doubl
   const Range R = uv_range(d.b);
 #define ROMS_UV_RHS(SINK) \
   hipLaunchKernelGGL((k_uvdiag_rhs<SINK>), grid_of(R), dim3(kBX, kBY), 0, s, d, R, nnew, nrhs, Uv.A, coef, cm1)
-  ROMS_UV_SINKS(sink, ROMS_UV_RHS);
+  ROMS_SINKS(sink, ROMS_UV_RHS);
 #undef ROMS_UV_RHS
 }
 void launch_hmx(const Dev& d, hipStream_t s, int nstp, int sink, double coef, double cm1) {
   const Range R = uv_range(d.b);
 #define ROMS_UV_HMX(SINK) \
   hipLaunchKernelGGL((k_uvdiag_hmx<SINK>), grid3_of(R, d.b.N), dim3(kBX, kBY), 0, s, d, R, nstp, Uv.A, coef, cm1)
-  ROMS_UV_SINKS(sink, ROMS_UV_HMX);
+  ROMS_SINKS(sink, ROMS_UV_HMX);
 #undef ROMS_UV_HMX
 }
 void launch_cpl(const Dev& d, hipStream_t s, int nnew, int sink, double coef, double cm1) {
   const Range R = uv_range(d.b);
 #define ROMS_UV_CPL(SINK) \
   hipLaunchKernelGGL((k_uvdiag_cpl<SINK>), grid3_of(R, 2), dim3(kBX, kBY), 0, s, d, R, nnew, Uv.A, coef, cm1)
-  ROMS_UV_SINKS(sink, ROMS_UV_CPL);
+  ROMS_SINKS(sink, ROMS_UV_CPL);
 #undef ROMS_UV_CPL
 }
 
-void fill_view() {
-  UvdView& V = Uv.view;
-  V = UvdView{};
-  V.armed = Uv.armed;
-  V.do_avg = Uv.avg;
+// the momentum variables of a diagnostics record (create_diagvars, diagnostics.F:812-889; wrt_diag_uv :923-962):
+// u_pgr .. u_cpl at u points, v_pgr .. v_cpl at v points, N levels
+std::vector<OutVar> uvdiag_vars(const ShimState& S) {
+  static const char* sfx[7] = {"_pgr", "_cor", "_adv", "_dis", "_hmx", "_vmx", "_cpl"};
+  static const char* lnm[7] = {"Hydrostatic Presssure Gradient", "Coriolis and Curvilinear", "Advection (Hor. and Vert.",
+                               "Numerical dissipation", "Horizontal mixing", "Vertical mixing", "2D/3D coupling"};
+  std::vector<OutVar> v;
   for (int c = 0; c < 2; c++)
-    for (int q = 0; q < kUvTerms; q++) V.term[c][q] = Uv.A.p[c * kUvTerms + q];
+    for (int a = 0; a < kUvTerms; a++)
+      v.push_back(out_var(S, std::string(c == 0 ? "u" : "v") + sfx[a], lnm[a], "m^2/s^2", c == 0 ? 'u' : 'v', S.d->b.N, 0,
+                          Uv.A.p[c * kUvTerms + a], S.d->b.n2));
+  return v;
 }
 
 }  // namespace
@@ -360,39 +347,26 @@ bool uvdiag_sampling() { return Uv.sampling; }
 void uvdiag_prsgrd(const Dev& d, hipStream_t s) { launch_snap_r(d, s); }
 
 void uvdiag_uv1_begin(const Dev& d, hipStream_t s, const Tlev& t) {
-  Uv.navg = Uv.avg ? Uv.navg + 1 : 1;
-  Uv.coef = 1.0 / (double)Uv.navg;
-  Uv.cm1 = 1.0 - Uv.coef;
+  Uv.w.open();
   Uv.open = true;
   Uv.hmx_done = Uv.cpl_done = false;
   launch_snap_q(d, s, t.nnew);
 }
 void uvdiag_uv1_end(const Dev& d, hipStream_t s, const Tlev& t) {
-  launch_rhs(d, s, t.nnew, t.nrhs, uv_sink(), Uv.coef, Uv.cm1);
+  launch_rhs(d, s, t.nnew, t.nrhs, Uv.w.sink(), Uv.w.coef, Uv.w.cm1);
 }
 void uvdiag_visc3d(const Dev& d, hipStream_t s, const Tlev& t) {
   if (!Uv.open || Uv.hmx_done) return;
   Uv.hmx_done = true;
-  launch_hmx(d, s, t.nstp, uv_sink(), Uv.coef, Uv.cm1);
+  launch_hmx(d, s, t.nstp, Uv.w.sink(), Uv.w.coef, Uv.w.cm1);
 }
 void uvdiag_uv2(const Dev& d, hipStream_t s, const Tlev& t) {
   if (!Uv.open || Uv.cpl_done) return;
   Uv.cpl_done = true;
   Uv.have = true;
-  launch_cpl(d, s, t.nnew, uv_sink(), Uv.coef, Uv.cm1);
+  launch_cpl(d, s, t.nnew, Uv.w.sink(), Uv.w.coef, Uv.w.cm1);
 }
 
-const UvdView& uvdiag_view() {
-  Uv.view.navg = Uv.navg;
-  Uv.view.have = Uv.have;
-  return Uv.view;
-}
-void uvdiag_window_written() {
-  if (!Uv.avg) return;
-  Uv.navg = 0;
-  Uv.have = false;
-  Uv.open = false;
-}
 void uvdiag_free() { uv_release(); }
 
 }  // namespace roms
@@ -426,9 +400,8 @@ int roms_gpu_uvdiag_begin(int on, int do_avg) {
   uv_release();
   for (int a = 0; a < kUvArr; a++) { Uv.base[a] = base[a]; Uv.A.p[a] = p[a]; }
   Uv.armed = true;
-  Uv.avg = do_avg != 0;
+  Uv.w.avg = do_avg != 0;
   Uv.sampling = true;
-  fill_view();
   return 0;
 }
 
@@ -446,8 +419,8 @@ int roms_gpu_uvdiag_state(int* armed, int* do_avg, int* navg, int* sampling) {
   int r = shim_enter(S, true);
   if (r) return r;
   if (armed) *armed = Uv.armed ? 1 : 0;
-  if (do_avg) *do_avg = Uv.avg ? 1 : 0;
-  if (navg) *navg = Uv.avg ? Uv.navg : 0;
+  if (do_avg) *do_avg = Uv.w.avg ? 1 : 0;
+  if (navg) *navg = Uv.w.reported();
   if (sampling) *sampling = Uv.sampling ? 1 : 0;
   return 0;
 }
@@ -473,11 +446,25 @@ int roms_gpu_wrt_diag(const char* path, int rec, int total_rec, double time, dou
   if (r) return r;
   if (!Uv.armed) { *S.err = "roms_gpu_wrt_diag: not armed (roms_gpu_uvdiag_begin)"; return -4; }
   if (!Uv.have) { *S.err = "roms_gpu_wrt_diag: no complete sample to write (no corrector reached step3d_uv2 while sampling)"; return -4; }
-  const TdiaView& tv = tdiag_view();
-  const bool trc = !tv.trc.empty();
-  if (trc && tv.do_avg != Uv.avg) { *S.err = "roms_gpu_wrt_diag: the momentum and the tracer terms disagree on do_avg"; return -1; }
-  if (trc && !tv.have) { *S.err = "roms_gpu_wrt_diag: the armed tracers have no sample to write"; return -4; }
-  return diag_write(path, rec, total_rec, time, period, t, uvdiag_view(), trc ? &tv : nullptr);
+  RecordSpec spec;
+  spec.vars = uvdiag_vars(S);   // create_diagvars' order: the momentum variables, then the tracers'
+  bool tavg, thave;
+  const bool trc = tdiag_record(S, spec.vars, &tavg, &thave);
+  if (trc && tavg != Uv.w.avg) { *S.err = "roms_gpu_wrt_diag: the momentum and the tracer terms disagree on do_avg"; return -1; }
+  if (trc && !thave) { *S.err = "roms_gpu_wrt_diag: the armed tracers have no sample to write"; return -4; }
+  spec.type = "ROMS diagnostics file";   // create_diagnostics_file (diagnostics.F:1006-1010)
+  // init_diagnostics (:231-234): what is in the file
+  spec.gatts.push_back({"diagnostic_options", std::string("Chosen Diagnostics = Momentum") + (trc ? ", Tracers" : "")});
+  if (Uv.w.avg) spec.gatts.push_back({"diag_avg_time", seconds_att(period)});   // :754-755
+  spec.time = time;
+  if ((r = write_record(S, path, rec, total_rec, t, spec))) return r;
+  if (trc) tdiag_window_written();   // diagnostics.F:778
+  if (Uv.w.avg) {
+    Uv.w.written();
+    Uv.have = false;
+    Uv.open = false;
+  }
+  return 0;
 }
 
 // n launches of each kernel group over the whole interior between two events on the library stream
@@ -493,27 +480,17 @@ int roms_gpu_time_uvdiag(int n, roms_tlev* t, double ms[4]) {
     return -1;
   }
   const Dev& d = *S.d;
-  const int sink = Uv.avg ? kUvMean : kUvStore;
-  hipEvent_t e[2];
-  if (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess) { *S.err = "roms_gpu_time_uvdiag: events"; return -2; }
-  for (int q = 0; q < 4; q++) ms[q] = 0.0;
-  for (int which = 0; which < 4 && !r; which++) {
-    for (int q = -1; q < n; q++) {   // q = -1: an untimed first launch
-      if (q == 0) (void)hipEventRecord(e[0], S.s);
+  const int sink = Uv.w.avg ? kMean : kStore;
+  for (int which = 0; which < 4; which++) {
+    ms[which] = time_rounds(S.s, n, true, [&]() {   // an untimed first launch
       if (which == 0) { launch_snap_r(d, S.s); launch_snap_q(d, S.s, t->nnew); }
       else if (which == 1) launch_rhs(d, S.s, t->nnew, t->nrhs, sink, 0.5, 0.5);
       else if (which == 2) launch_hmx(d, S.s, t->nstp, sink, 0.5, 0.5);
       else launch_cpl(d, S.s, t->nnew, sink, 0.5, 0.5);
-    }
-    (void)hipEventRecord(e[1], S.s);
-    float f = 0.f;
-    if (hipEventSynchronize(e[1]) != hipSuccess || hipEventElapsedTime(&f, e[0], e[1]) != hipSuccess) r = -2;
-    if (hipGetLastError() != hipSuccess) r = -3;
-    ms[which] = (double)f;
+      return 0;
+    });
+    if (ms[which] < 0) { *S.err = "roms_gpu_time_uvdiag: launch or timing failed"; return (int)ms[which]; }
   }
-  (void)hipEventDestroy(e[0]);
-  (void)hipEventDestroy(e[1]);
-  if (r) { *S.err = "roms_gpu_time_uvdiag: launch or timing failed"; return r; }
   return 0;
 }
 

@@ -35,13 +35,6 @@
 namespace roms {
 namespace {
 
-template <int SINK>
-__device__ __forceinline__ void wvl_put(double* __restrict__ p, double w, double coef, double cm1) {
-  if (SINK == kWvlStore) *p = w;
-  else if (SINK == kWvlMeanFirst) *p = w * coef;
-  else *p = *p * cm1 + w * coef;
-}
-
 // R: the computed range imin..imax x jmin..jmax; off: (nstp-1)*n3; out: element IJ = 0 of level 1
 template <int SINK, bool VG>
 __global__ void __launch_bounds__(256) k_wvlcty(Dev d, Range R, long off, double* __restrict__ out, double coef,
@@ -54,23 +47,23 @@ __global__ void __launch_bounds__(256) k_wvlcty(Dev d, Range R, long off, double
   // gradient copies (wvlcty.F:138-191): physical edges only, none in a periodic direction
   const bool cw = b.west_edge && i == R.i0, ce = b.east_edge && i == R.i1;
   const bool cs = b.south_edge && j == R.j0, cn = b.north_edge && j == R.j1;
-  // old: the lane's own old mean of level k, loaded a level ahead with the level's other loads (kWvlMean);
+  // old: the lane's own old mean of level k, loaded a level ahead with the level's other loads (kMean);
   // the copies next to an edge column update theirs in place
   auto emit = [&](int k, double w, double old) {
     double* __restrict__ o = out + ij + (long)(k - 1) * n2;
-    if (SINK == kWvlMean) *o = old * cm1 + w * coef;
-    else wvl_put<SINK>(o, w, coef, cm1);
-    if (cw) wvl_put<SINK>(o - 1, w, coef, cm1);
-    if (ce) wvl_put<SINK>(o + 1, w, coef, cm1);
+    if (SINK == kMean) *o = old * cm1 + w * coef;
+    else sink_put<SINK>(o, w, coef, cm1);
+    if (cw) sink_put<SINK>(o - 1, w, coef, cm1);
+    if (ce) sink_put<SINK>(o + 1, w, coef, cm1);
     if (cs) {
-      wvl_put<SINK>(o - nx, w, coef, cm1);
-      if (cw) wvl_put<SINK>(o - nx - 1, w, coef, cm1);
-      if (ce) wvl_put<SINK>(o - nx + 1, w, coef, cm1);
+      sink_put<SINK>(o - nx, w, coef, cm1);
+      if (cw) sink_put<SINK>(o - nx - 1, w, coef, cm1);
+      if (ce) sink_put<SINK>(o - nx + 1, w, coef, cm1);
     }
     if (cn) {
-      wvl_put<SINK>(o + nx, w, coef, cm1);
-      if (cw) wvl_put<SINK>(o + nx - 1, w, coef, cm1);
-      if (ce) wvl_put<SINK>(o + nx + 1, w, coef, cm1);
+      sink_put<SINK>(o + nx, w, coef, cm1);
+      if (cw) sink_put<SINK>(o + nx - 1, w, coef, cm1);
+      if (ce) sink_put<SINK>(o + nx + 1, w, coef, cm1);
     }
   };
   const double pm0 = F.pm[ij], pn0 = F.pn[ij];
@@ -89,12 +82,12 @@ __global__ void __launch_bounds__(256) k_wvlcty(Dev d, Range R, long off, double
   const double* __restrict__ ZR = F.z_r + ij;
   double wm1 = 0.0, wm2 = 0.0, wm3 = 0.0;   // Wrk(k-1), Wrk(k-2), Wrk(k-3); Wrk(0) = 0
   double sl1 = 0.0;                          // the slope term of level k-1
-  double oldtop = 0.0;                       // the old mean of level N (kWvlMean)
+  double oldtop = 0.0;                       // the old mean of level N (kMean)
 #pragma unroll 2
   for (int k = 1; k <= N; k++) {
     const long o = (long)(k - 1) * n2;
     double old = 0.0, oldN = 0.0;
-    if (SINK == kWvlMean) {
+    if (SINK == kMean) {
       if (k >= 2) old = out[ij + o - n2];
       if (k == N) oldN = out[ij + o];
     }
@@ -160,9 +153,7 @@ int wvl_launch(const ShimState& S, int nstp, double* out, int sink, double coef,
     if (vg) hipLaunchKernelGGL((k_wvlcty<SINK, true>), grid, blk, 0, S.s, d, R, off, out, coef, cm1);      \
     else hipLaunchKernelGGL((k_wvlcty<SINK, false>), grid, blk, 0, S.s, d, R, off, out, coef, cm1);        \
   } while (0)
-  if (sink == kWvlStore) ROMS_WVL_GO(kWvlStore);
-  else if (sink == kWvlMeanFirst) ROMS_WVL_GO(kWvlMeanFirst);
-  else ROMS_WVL_GO(kWvlMean);
+  ROMS_SINKS(sink, ROMS_WVL_GO);
 #undef ROMS_WVL_GO
   if (hipGetLastError() != hipSuccess) { *S.err = "wvlcty: launch failed"; return -3; }
   return 0;
@@ -170,12 +161,12 @@ int wvl_launch(const ShimState& S, int nstp, double* out, int sink, double coef,
 
 const double* wvl_compute(const ShimState& S, int nstp, int* rc) {
   *rc = 0;
-  if (S.d->b.N < 2) { *rc = wvl_launch(S, nstp, nullptr, kWvlStore, 1.0, 0.0); return nullptr; }
+  if (S.d->b.N < 2) { *rc = wvl_launch(S, nstp, nullptr, kStore, 1.0, 0.0); return nullptr; }
   if (!Wv.p) {
     Wv.p = wvl_alloc_like_u(*S.d, S.s, &Wv.base);
     if (!Wv.p) { *S.err = "wvlcty: allocation of the work array failed"; *rc = -2; return nullptr; }
   }
-  if ((*rc = wvl_launch(S, nstp, Wv.p, kWvlStore, 1.0, 0.0))) return nullptr;
+  if ((*rc = wvl_launch(S, nstp, Wv.p, kStore, 1.0, 0.0))) return nullptr;
   Wv.have = true;
   return Wv.p;
 }
@@ -224,23 +215,13 @@ int roms_gpu_time_wvlcty(int n, const roms_tlev* t, double* ms) {
   if (!tlev_ok(t) || n < 1 || !ms) { *S.err = "roms_gpu_time_wvlcty: bad arguments"; return -1; }
   (void)wvl_compute(S, t->nstp, &r);   // allocates; an untimed first launch
   if (r) return r;
-  hipEvent_t e[2];
-  if (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess) { *S.err = "roms_gpu_time_wvlcty: events"; return -2; }
   double* mean = avg_view().wvl;
-  ms[0] = ms[1] = 0.0;
-  for (int sink = 0; sink < 2 && !r; sink++) {
-    if (sink == 1 && !mean) break;
-    (void)hipEventRecord(e[0], S.s);
-    for (int q = 0; q < n && !r; q++)
-      r = sink == 0 ? wvl_launch(S, t->nstp, Wv.p, kWvlStore, 1.0, 0.0) : wvl_launch(S, t->nstp, mean, kWvlMean, 0.5, 0.5);
-    (void)hipEventRecord(e[1], S.s);
-    float f = 0.f;
-    if (hipEventSynchronize(e[1]) != hipSuccess || hipEventElapsedTime(&f, e[0], e[1]) != hipSuccess) r = r ? r : -2;
-    ms[sink] = (double)f;
+  ms[0] = time_rounds(S.s, n, false, [&]() { return wvl_launch(S, t->nstp, Wv.p, kStore, 1.0, 0.0); });
+  ms[1] = mean && ms[0] >= 0 ? time_rounds(S.s, n, false, [&]() { return wvl_launch(S, t->nstp, mean, kMean, 0.5, 0.5); }) : 0.0;
+  if (ms[0] < 0 || ms[1] < 0) {
+    *S.err = "roms_gpu_time_wvlcty: launch or timing failed";
+    return (int)(ms[0] < 0 ? ms[0] : ms[1]);
   }
-  (void)hipEventDestroy(e[0]);
-  (void)hipEventDestroy(e[1]);
-  if (r) { *S.err = "roms_gpu_time_wvlcty: launch or timing failed"; return r; }
   return 0;
 }
 

@@ -192,7 +192,14 @@ struct ZslBuf {
 };
 
 struct ZslCtx {
-  ZslView v;                      // what rst_io.hip's writer sees
+  // ndep planes per sliced field in the 2-D device layout, zero outside cells 1..Lm x 1..Mm
+  int what = 0;                   // ROMS_ZSL_* bits armed (0: slicing off)
+  int ndep = 0;
+  MeanWindow w;                   // w.avg: the means are kept (do_avg)
+  std::vector<double> vecdep;
+  std::vector<int> trc;           // tracer index (1..NT) of each sliced tracer
+  std::vector<double*> t, t_avg;  // one per sliced tracer
+  double *u = nullptr, *v = nullptr, *u_avg = nullptr, *v_avg = nullptr;
   std::vector<ZslBuf> bufs;
   std::vector<ZslField> fields;   // host copy of the table
   ZslField* d_tab = nullptr;
@@ -218,7 +225,7 @@ double* zsl_alloc(const double* like, long n, hipStream_t s) {
   return b.p;
 }
 
-int zsl_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) {
+int zsl_launch(const ShimState& S, const roms_tlev& t) {
   const Bounds& b = S.d->b;
   ZslArgs a{};
   a.tab = Z.d_tab;
@@ -228,14 +235,14 @@ int zsl_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) 
     a.count[g] = Z.count[g];
     if (Z.count[g]) a.types[nz++] = g;
   }
-  a.ndep = Z.v.ndep;
+  a.ndep = Z.ndep;
   a.slot_off = (long)(t.nnew - 1) * b.n3;
-  a.coef = coef;
-  a.cm1 = cm1;
-  for (int m = 0; m < Z.v.ndep; m++) a.dep[m] = Z.v.vecdep[m];
+  a.coef = Z.w.coef;
+  a.cm1 = Z.w.cm1;
+  for (int m = 0; m < Z.ndep; m++) a.dep[m] = Z.vecdep[m];
   const Range R{1, b.Lm, 1, b.Mm};
   const dim3 grid = grid3_of(R, nz), blk(kBX, kBY);
-  const bool vg = shim_vgrid_valid(), first = !Z.v.do_avg || coef == 1.0;
+  const bool vg = shim_vgrid_valid(), first = Z.w.sink() != kMean;
   if (vg && first) hipLaunchKernelGGL((k_zslice<true, true>), grid, blk, 0, S.s, *S.d, R, a);
   else if (vg) hipLaunchKernelGGL((k_zslice<true, false>), grid, blk, 0, S.s, *S.d, R, a);
   else if (first) hipLaunchKernelGGL((k_zslice<false, true>), grid, blk, 0, S.s, *S.d, R, a);
@@ -245,10 +252,34 @@ int zsl_launch(const ShimState& S, const roms_tlev& t, double coef, double cm1) 
 
 // one sample: the slices, and with do_avg the means' next step
 int zsl_sample(const ShimState& S, const roms_tlev& t) {
-  const double coef = Z.v.do_avg ? 1.0 / (double)(Z.v.navg + 1) : 1.0;
-  const int r = zsl_launch(S, t, coef, 1.0 - coef);
-  if (!r && Z.v.do_avg) Z.v.navg += 1;
+  const MeanWindow before = Z.w;
+  Z.w.open();
+  const int r = zsl_launch(S, t);
+  if (r) Z.w = before;
   return r;
+}
+
+// the variable list of a slices record (def_vars_zslice): each sliced tracer
+// under its name, u, v, ndep planes each (the means with do_avg).  The reference writes 'averaged'
+// straight ahead of a tracer's long name and 'averaged ' ahead of u's and v's
+std::vector<OutVar> zslice_vars(const ShimState& S) {
+  const bool avg = Z.w.avg;
+  const long n2 = S.d->b.n2;
+  std::vector<OutVar> v;
+  if (Z.what & ROMS_ZSL_T) {
+    std::vector<std::string> nm, un, ln;
+    io_tracer_meta(S, nm, un, ln);
+    for (size_t q = 0; q < Z.trc.size(); q++) {
+      const int it = Z.trc[q] - 1;
+      v.push_back(out_var(S, nm[it], avg ? "averaged" + ln[it] : ln[it], un[it], 'r', 0, Z.ndep, avg ? Z.t_avg[q] : Z.t[q], n2));
+    }
+  }
+  const std::string av = avg ? "averaged " : "";
+  if (Z.what & ROMS_ZSL_U)
+    v.push_back(out_var(S, "u", av + "u-momentum component", "meter second-1", 'u', 0, Z.ndep, avg ? Z.u_avg : Z.u, n2));
+  if (Z.what & ROMS_ZSL_V)
+    v.push_back(out_var(S, "v", av + "v-momentum component", "meter second-1", 'v', 0, Z.ndep, avg ? Z.v_avg : Z.v, n2));
+  return v;
 }
 
 bool zsl_tlev_ok(const roms_tlev* t) { return t && t->nnew >= 1 && t->nnew <= 3; }
@@ -286,7 +317,7 @@ int roms_gpu_zslice_begin(int what, int ndep, const double* vecdep, int nt_z, co
       }
   }
   zsl_release();
-  ZslView& V = Z.v;
+  ZslCtx& V = Z;
   const long n = (long)ndep * b.n2;
   bool oom = false;
   auto add = [&](const double* src, double*& out, double*& avg) {
@@ -320,8 +351,7 @@ int roms_gpu_zslice_begin(int what, int ndep, const double* vecdep, int nt_z, co
   }
   V.what = what;
   V.ndep = ndep;
-  V.do_avg = do_avg != 0;
-  V.navg = 0;
+  V.w.avg = do_avg != 0;
   V.vecdep.assign(vecdep, vecdep + ndep);
   return 0;
 }
@@ -330,7 +360,7 @@ int roms_gpu_calc_zslice(const roms_tlev* t) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  if (!Z.v.what) { *S.err = "roms_gpu_calc_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
+  if (!Z.what) { *S.err = "roms_gpu_calc_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
   if (!zsl_tlev_ok(t)) { *S.err = "roms_gpu_calc_zslice: bad time levels"; return -1; }
   if ((r = zsl_sample(S, *t))) { *S.err = "roms_gpu_calc_zslice: launch failed"; return r; }
   return 0;
@@ -340,12 +370,17 @@ int roms_gpu_wrt_zslice(const char* path, int rec, int total_rec, double time, c
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  if (!Z.v.what) { *S.err = "roms_gpu_wrt_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
+  if (!Z.what) { *S.err = "roms_gpu_wrt_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
   if (!path || rec < 1 || !zsl_tlev_ok(t)) { *S.err = "roms_gpu_wrt_zslice: bad path/record/time levels"; return -1; }
-  if (Z.v.do_avg && Z.v.navg == 0) { *S.err = "roms_gpu_wrt_zslice: no sample in the window (roms_gpu_calc_zslice)"; return -4; }
-  if (!Z.v.do_avg && (r = zsl_sample(S, *t))) { *S.err = "roms_gpu_wrt_zslice: launch failed"; return r; }
-  if ((r = zslice_write(path, rec, total_rec, time, t, Z.v))) return r;
-  Z.v.navg = 0;   // the next sample starts a fresh window (zslice_output.F:406)
+  if (Z.w.avg && !Z.w.have) { *S.err = "roms_gpu_wrt_zslice: no sample in the window (roms_gpu_calc_zslice)"; return -4; }
+  if (!Z.w.avg && (r = zsl_sample(S, *t))) { *S.err = "roms_gpu_wrt_zslice: launch failed"; return r; }
+  RecordSpec spec;
+  spec.type = "ROMS zslice file";
+  spec.time = time;
+  spec.depths = Z.vecdep;
+  spec.vars = zslice_vars(S);
+  if ((r = write_record(S, path, rec, total_rec, t, spec))) return r;
+  Z.w.written();   // the next sample starts a fresh window (zslice_output.F:406)
   return 0;
 }
 
@@ -353,10 +388,10 @@ int roms_gpu_zslice_state(int* navg, int* what, int* ndep, int* do_avg) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  if (navg) *navg = Z.v.navg;
-  if (what) *what = Z.v.what;
-  if (ndep) *ndep = Z.v.ndep;
-  if (do_avg) *do_avg = Z.v.do_avg ? 1 : 0;
+  if (navg) *navg = Z.w.reported();
+  if (what) *what = Z.what;
+  if (ndep) *ndep = Z.ndep;
+  if (do_avg) *do_avg = Z.w.avg ? 1 : 0;
   return 0;
 }
 
@@ -364,7 +399,8 @@ int roms_gpu_zslice_copy_out(int what_bit, int q, double* dst, long count) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  const ZslView& V = Z.v;
+  const ZslCtx& V = Z;
+  const bool do_avg = V.w.avg;
   if (what_bit != ROMS_ZSL_T && what_bit != ROMS_ZSL_U && what_bit != ROMS_ZSL_V) {
     *S.err = "roms_gpu_zslice_copy_out: what_bit must be one ROMS_ZSL_* bit";
     return -1;
@@ -373,11 +409,11 @@ int roms_gpu_zslice_copy_out(int what_bit, int q, double* dst, long count) {
   const double* p = nullptr;
   if (what_bit == ROMS_ZSL_T) {
     if (q < 1 || q > (int)V.t.size()) { *S.err = "roms_gpu_zslice_copy_out: no such sliced tracer"; return -1; }
-    p = V.do_avg ? V.t_avg[q - 1] : V.t[q - 1];
+    p = do_avg ? V.t_avg[q - 1] : V.t[q - 1];
   } else if (what_bit == ROMS_ZSL_U) {
-    p = V.do_avg ? V.u_avg : V.u;
+    p = do_avg ? V.u_avg : V.u;
   } else {
-    p = V.do_avg ? V.v_avg : V.v;
+    p = do_avg ? V.v_avg : V.v;
   }
   const long rows = (long)V.ndep * (S.d->b.Mm + 4);
   if (count != rows * (S.d->b.Lm + 4)) { *S.err = "roms_gpu_zslice_copy_out: count is not ndep*(Mm+4)*(Lm+4)"; return -1; }
@@ -392,19 +428,11 @@ int roms_gpu_time_calc_zslice(int n, const roms_tlev* t, double* ms) {
   ShimState S;
   int r = shim_enter(S, true);
   if (r) return r;
-  if (!Z.v.what) { *S.err = "roms_gpu_time_calc_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
+  if (!Z.what) { *S.err = "roms_gpu_time_calc_zslice: slicing is not armed (roms_gpu_zslice_begin)"; return -4; }
   if (!zsl_tlev_ok(t) || n < 1 || !ms) { *S.err = "roms_gpu_time_calc_zslice: bad arguments"; return -1; }
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { *S.err = "roms_gpu_time_calc_zslice: events"; return -2; }
-  (void)hipEventRecord(e0, S.s);
-  for (int q = 0; q < n && !r; q++) r = zsl_sample(S, *t);
-  (void)hipEventRecord(e1, S.s);
-  float f = 0.f;
-  if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&f, e0, e1) != hipSuccess) r = r ? r : -2;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (r) { *S.err = "roms_gpu_time_calc_zslice: launch or timing failed"; return r; }
-  *ms = (double)f;
+  const double f = time_rounds(S.s, n, false, [&]() { return zsl_sample(S, *t); });
+  if (f < 0) { *S.err = "roms_gpu_time_calc_zslice: launch or timing failed"; return (int)f; }
+  *ms = f;
   return 0;
 }
 

@@ -14,15 +14,21 @@
 // joins the writer; a new write joins the previous one first (one staging
 // buffer).  Reads (get_init) are synchronous: host read, masking as the
 // reference does it, upload of packed slabs, one scatter kernel per variable,
-// and the reference's exchange_xxx after every field.  Averages records
-// (wrt_avg_ocean_vars, basic_output.F:421-515) take the same write path with
-// the running means of k_avg.hip in place of the fields, and slices records
-// (zslice_output.F:284-410) with the planes of k_zslice.hip on a depth
-// dimension in place of s_rho.
+// and the reference's exchange_xxx after every field.
+//
+// write_record knows no producer: it takes a RecordSpec (shim_state.h) -- the
+// file's type, the attributes after it, the variables, the depths of a depth
+// dimension, ocean_time -- and each producer builds its own next to the arrays
+// it names: restart, history and averages records (wrt_avg_ocean_vars,
+// basic_output.F:421-515: the running means of k_avg.hip in place of the
+// fields) here, slices (zslice_output.F:284-410) in k_zslice.hip, the budget
+// terms in k_tdiag.hip and k_uvdiag.hip.  The extraction file defines itself
+// (extract_write) and shares start_job, the drain and the writer thread.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -36,19 +42,6 @@
 
 namespace roms {
 namespace {
-
-// one (i0:i1, j0:j1, 1:nk) block of a device field, packed i fastest
-struct Slab {
-  const double* src;   // element (i0, j0, level 1)
-  int ni, nj, nk;
-  long sj, sk;         // row and level strides
-  int as_mask;         // riv_umask/riv_vmask: 1 where the river face array is non-zero
-  // history omega (basic_output.F:374-384): pm*pn*(We+Wi) in m/s when src2
-  // (Wi) is set; pm/pn are 2-D, element (i0, j0).  Averages omega
-  // (basic_output.F:482): src is w_avg, src2 unset, (w_avg*pm)*pn in that order
-  const double* src2;
-  const double *pm, *pn;
-};
 
 __global__ void __launch_bounds__(256) k_io_pack(Slab s, double* __restrict__ dst) {
   const long n = (long)s.ni * s.nj * s.nk;
@@ -106,15 +99,6 @@ Slab slab_of(const Bounds& b, const Part& p, const double* base, char g, int nk,
   return s;
 }
 
-struct OutVar {
-  std::string name, lname, units;
-  char grid;      // 'r', 'u', 'v'
-  int levels;     // 0: 2-D; N or N+1
-  int depth = 0;  // slices: planes on the depth dimension (levels 0)
-  Slab slab;
-  long off = 0;   // offset in the staging buffer (elements)
-};
-
 struct IoJob {
   std::thread th;
   bool running = false;
@@ -140,26 +124,6 @@ int io_join(std::string& err) {
   io.job.running = false;
   if (io.job.status) { err = io.job.err; return io.job.status; }
   return 0;
-}
-
-// tracer names (tracers.F:296-301: temp, salt with SALINITY; passive tracers
-// get trcNN unless the host named them with roms_gpu_io_tracer_name)
-void tracer_meta(int NT, bool salinity, std::vector<std::string>& nm, std::vector<std::string>& un,
-                 std::vector<std::string>& ln) {
-  nm.assign(NT, ""); un.assign(NT, ""); ln.assign(NT, "");
-  for (int q = 0; q < NT; q++) {
-    if ((size_t)q < io.tname.size() && !io.tname[q].empty()) {
-      nm[q] = io.tname[q]; un[q] = io.tunits[q]; ln[q] = io.tlname[q];
-    } else if (q == 0) {
-      nm[q] = "temp"; un[q] = "Celsius"; ln[q] = "potential temperature";
-    } else if (q == 1 && salinity) {
-      nm[q] = "salt"; un[q] = "PSU"; ln[q] = "salinity";
-    } else {
-      char b[32];
-      snprintf(b, sizeof b, "trc%02d", q + 1);
-      nm[q] = b; un[q] = "nondim"; ln[q] = std::string("passive tracer ") + b;
-    }
-  }
 }
 
 // put_global_atts (roms_read_write.F:1544-1660) + the 'type' attribute of the creator
@@ -207,15 +171,10 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
                                 const double* wvl = nullptr) {
   const Bounds& b = S.d->b;
   const Fields& F = S.d->f;
-  const Part p = part_of(*S.dims);
   const int N = b.N;
   std::vector<OutVar> v;
-  auto add = [&](const char* name, const char* ln, const char* un, char g, int lev, const double* base, long sk) {
-    OutVar o;
-    o.name = name; o.lname = av ? std::string("averaged ") + ln : std::string(ln); o.units = un; o.grid = g; o.levels = lev;
-    o.slab = slab_of(b, p, base, g, lev ? lev : 1, sk);
-    v.push_back(o);
-  };
+  auto add = [&](const std::string& name, const std::string& ln, const std::string& un, char g, int lev, const double* base,
+                 long sk) { v.push_back(out_var(S, name, av ? "averaged " + ln : ln, un, g, lev, 0, base, sk)); };
   const long n2 = b.n2;
   const int knew = t.knew, nnew = t.nnew;
   if (rst || (mask & ROMS_WRT_Z)) add("zeta", "free-surface elevation", "meter", 'r', 0, av ? av->zeta : F.zeta + (knew - 1) * n2, 0);
@@ -227,13 +186,9 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   if (rst || (mask & ROMS_WRT_V)) add("v", "v-momentum component", "meter second-1", 'v', N, av ? av->v : F.v + (nnew - 1) * b.n3, n2);
   if (rst || (mask & ROMS_WRT_T)) {
     std::vector<std::string> nm, un, ln;
-    tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
-    for (int q = 0; q < b.NT; q++) {
-      OutVar o;
-      o.name = nm[q]; o.lname = av ? "averaged " + ln[q] : ln[q]; o.units = un[q]; o.grid = 'r'; o.levels = N;
-      o.slab = slab_of(b, p, av ? av->t[q] : F.t + (long)(nnew - 1) * b.n3 + (long)q * 3 * b.n3, 'r', N, n2);
-      v.push_back(o);
-    }
+    io_tracer_meta(S, nm, un, ln);
+    for (int q = 0; q < b.NT; q++)
+      add(nm[q], ln[q], un[q], 'r', N, av ? av->t[q] : F.t + (long)(nnew - 1) * b.n3 + (long)q * 3 * b.n3, n2);
   }
   if (rst) {   // EXACT_RESTART + EXTRAP_BAR_FLUXES (basic_output.F:634-642)
     add("DU_avg1", "<<fast-time averaged uflx>>", "", 'u', 0, F.DU_avg1, 0);
@@ -255,7 +210,7 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
     o.pn = F.pn + off;
   }
   // true vertical velocity (wvlcty.F; basic_output.F:386-392, 486, defined :816-822 between omega and AKv):
-  // history takes the work array write_record filled just before, averages the running mean
+  // history takes the work array roms_gpu_wrt_his filled just before, averages the running mean
   if (!rst && (mask & ROMS_WRT_W) && (av ? av->wvl : wvl)) add("w", "vertical velocity", "meter second-1", 'r', N, av ? av->wvl : wvl, n2);
   if (!rst && (mask & ROMS_WRT_AKV)) add("AKv", "vertical viscosity coefficient", "meter2 second-1", 'r', N + 1, av ? av->akv : F.Akv, n2);
   if (!rst && (mask & ROMS_WRT_AKT))
@@ -275,110 +230,26 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   return v;
 }
 
-// the variable list of a slices record (def_vars_zslice): each sliced tracer
-// under its name, u, v, ndep planes each.  The reference writes 'averaged'
-// straight ahead of a tracer's long name and 'averaged ' ahead of u's and v's
-std::vector<OutVar> zslice_vars(const ShimState& S, const ZslView& zv) {
-  const Bounds& b = S.d->b;
-  const Part p = part_of(*S.dims);
-  std::vector<OutVar> v;
-  auto add = [&](const std::string& name, const std::string& ln, const std::string& un, char g, const double* base) {
-    OutVar o;
-    o.name = name; o.lname = ln; o.units = un; o.grid = g; o.levels = 0; o.depth = zv.ndep;
-    o.slab = slab_of(b, p, base, g, zv.ndep, b.n2);
-    v.push_back(o);
-  };
-  if (zv.what & ROMS_ZSL_T) {
-    std::vector<std::string> nm, un, ln;
-    tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
-    for (size_t q = 0; q < zv.trc.size(); q++) {
-      const int it = zv.trc[q] - 1;
-      add(nm[it], zv.do_avg ? "averaged" + ln[it] : ln[it], un[it], 'r', zv.do_avg ? zv.t_avg[q] : zv.t[q]);
-    }
-  }
-  const std::string av = zv.do_avg ? "averaged " : "";
-  if (zv.what & ROMS_ZSL_U) add("u", av + "u-momentum component", "meter second-1", 'u', zv.do_avg ? zv.u_avg : zv.u);
-  if (zv.what & ROMS_ZSL_V) add("v", av + "v-momentum component", "meter second-1", 'v', zv.do_avg ? zv.v_avg : zv.v);
-  return v;
-}
-
-// the variable list of a diagnostics record (create_diagvars, diagnostics.F:891-921; wrt_diag_trc :964-991): per
-// armed tracer <name>_advx, _advy, _advz, _mixx, _mixy, _mixz, N levels at rho points
-std::vector<OutVar> tdiag_vars(const ShimState& S, const TdiaView& tv) {
-  const Bounds& b = S.d->b;
-  const Part p = part_of(*S.dims);
-  static const char* sfx[6] = {"_advx", "_advy", "_advz", "_mixx", "_mixy", "_mixz"};
-  static const char* lnm[6] = {"x-advective flux", "y-advective flux", "z-advective flux", "mixing x-flux", "mixing y-flux",
-                               "mixing z-flux"};
-  std::vector<std::string> nm, un, ln;
-  tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
-  std::vector<OutVar> v;
-  for (size_t q = 0; q < tv.trc.size(); q++)
-    for (int a = 0; a < 6; a++) {
-      OutVar o;
-      o.name = nm[tv.trc[q] - 1] + sfx[a]; o.lname = lnm[a]; o.units = "C m^3/s"; o.grid = 'r'; o.levels = b.N;
-      o.slab = slab_of(b, p, tv.term[a][q], 'r', b.N, b.n2);
-      v.push_back(o);
-    }
-  return v;
-}
-
-// the momentum variables of a diagnostics record (create_diagvars, diagnostics.F:812-889; wrt_diag_uv :923-962):
-// u_pgr .. u_cpl at u points, v_pgr .. v_cpl at v points, N levels
-std::vector<OutVar> uvdiag_vars(const ShimState& S, const UvdView& uv) {
-  const Bounds& b = S.d->b;
-  const Part p = part_of(*S.dims);
-  static const char* sfx[7] = {"_pgr", "_cor", "_adv", "_dis", "_hmx", "_vmx", "_cpl"};
-  static const char* lnm[7] = {"Hydrostatic Presssure Gradient", "Coriolis and Curvilinear", "Advection (Hor. and Vert.",
-                               "Numerical dissipation", "Horizontal mixing", "Vertical mixing", "2D/3D coupling"};
-  std::vector<OutVar> v;
-  for (int c = 0; c < 2; c++)
-    for (int a = 0; a < 7; a++) {
-      OutVar o;
-      o.name = std::string(c == 0 ? "u" : "v") + sfx[a]; o.lname = lnm[a]; o.units = "m^2/s^2";
-      o.grid = c == 0 ? 'u' : 'v'; o.levels = b.N;
-      o.slab = slab_of(b, p, uv.term[c][a], o.grid, b.N, b.n2);
-      v.push_back(o);
-    }
-  return v;
-}
-
-void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& vars, bool rst, bool avg = false,
-                 double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr,
-                 const UvdView* uv = nullptr) {
+void define_file(nc::File& f, const ShimState& S, const RecordSpec& spec) {
   const Part p = part_of(*S.dims);
   const int N = S.d->b.N;
   // create_file (roms_read_write.F:1161-1208): ocean_time first, then the global attributes
   const int dtm = f.add_dim("time", 0);
   f.add_var("ocean_time", nc::NC_DOUBLE, {dtm},
             {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
-  global_atts(f, S, rst ? "ROMS restart file" : avg ? "ROMS averages file" : zv ? "ROMS zslice file" : (tv || uv) ? "ROMS diagnostics file" : "ROMS history file");
-  if (tv || uv) {   // create_diagnostics_file (diagnostics.F:1006-1010); diag_avg_time as F12.1, left-adjusted (:754-755)
-    // init_diagnostics (:231-234): what is in the file
-    f.gatts.push_back(nc::Att::str("diagnostic_options", std::string("Chosen Diagnostics = ") + (uv ? "Momentum" : "") +
-                                                             (tv ? ", Tracers" : "")));
-    if (uv ? uv->do_avg : tv->do_avg) {
-      char tb[64];
-      snprintf(tb, sizeof tb, "%.1f seconds", period);
-      f.gatts.push_back(nc::Att::str("diag_avg_time", tb));
-    }
-  }
-  if (avg) {   // the window length as F12.1, left-adjusted (basic_output.F:451-455, 705)
-    char tb[64];
-    snprintf(tb, sizeof tb, "%.1f seconds", period);
-    f.gatts.push_back(nc::Att::str("averaging_timescale", tb));
-  }
+  global_atts(f, S, spec.type.c_str());
+  for (const auto& a : spec.gatts) f.gatts.push_back(nc::Att::str(a.first, a.second));
   const int daux = f.add_dim("auxil", 6);   // iaux
   f.add_var("time_step", nc::NC_INT, {dtm, daux},
             {nc::Att::str("long_name", "time step and record numbers from initialization")});
   const int dxr = f.add_dim("xi_rho", p.xi_rho), dxu = f.add_dim("xi_u", p.xi_u);
   const int dyr = f.add_dim("eta_rho", p.eta_rho), dyv = f.add_dim("eta_v", p.eta_v);
   int dzr = -1, dzw = -1, ddp = -1;
-  if (zv) {   // def_vars_zslice: depth(depth) = vecdep
-    ddp = f.add_dim("depth", zv->ndep);
+  if (!spec.depths.empty()) {   // def_vars_zslice: depth(depth) = vecdep
+    ddp = f.add_dim("depth", (int)spec.depths.size());
     f.add_var("depth", nc::NC_DOUBLE, {ddp});
   }
-  for (const OutVar& o : vars) {
+  for (const OutVar& o : spec.vars) {
     const int dx = o.grid == 'u' ? dxu : dxr, dy = o.grid == 'v' ? dyv : dyr;
     std::vector<int> dims{dtm};
     if (o.levels == N) { if (dzr < 0) dzr = f.add_dim("s_rho", N); dims.push_back(dzr); }
@@ -392,81 +263,36 @@ void define_file(nc::File& f, const ShimState& S, const std::vector<OutVar>& var
   }
 }
 
-int write_record(const char* path, int rec, int total_rec, double time, const roms_tlev* t, bool rst, int mask,
-                 bool avg = false, double period = 0.0, const ZslView* zv = nullptr, const TdiaView* tv = nullptr,
-                 const UvdView* uv = nullptr) {
-  ShimState S;
-  int r = shim_enter(S, true);
-  if (r) return r;
-  if (!path || rec < 1 || !t) { *S.err = "roms_gpu_wrt: bad path/record/time levels"; return -1; }
-  const AvgView* av = nullptr;
-  if (avg) {   // wrt_avg_ocean_vars: the open window's means, ocean_time = their mean time
-    av = &avg_view();
-    if (!av->mask) { *S.err = "roms_gpu_wrt_avg: averaging is not armed (roms_gpu_avg_begin)"; return -4; }
-    if (av->navg == 0) { *S.err = "roms_gpu_wrt_avg: no sample in the window (roms_gpu_calc_avg)"; return -4; }
-    mask = av->mask;
-    time = av->t_avg;
-  }
-  if ((r = io_join(*S.err))) return r;
-  const double* wvl = nullptr;
-  if (!rst && !avg && !zv && !tv && !uv && (mask & ROMS_WRT_W)) {   // call wvlcty (0, work), basic_output.F:390
-    if (t->nstp < 1 || t->nstp > 3) { *S.err = "roms_gpu_wrt_his: bad time levels"; return -1; }
-    wvl = wvl_compute(S, t->nstp, &r);
-    if (r) return r;
-  }
-  std::vector<OutVar> vars = uv ? uvdiag_vars(S, *uv) : tv ? tdiag_vars(S, *tv) : zv ? zslice_vars(S, *zv)
-                                                                                   : record_vars(S, *t, rst, mask, av, wvl);
-  if (uv && tv) {   // create_diagvars' order: the momentum variables, then the tracers'
-    const std::vector<OutVar> tvars = tdiag_vars(S, *tv);
-    vars.insert(vars.end(), tvars.begin(), tvars.end());
-  }
-  size_t n = 0;
-  for (OutVar& o : vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
+// What the record writer and the extraction writer share.  The n doubles at `dev`, complete once the library
+// stream reaches this point, are copied to pinned host memory on the drain stream (created on first use) while
+// the model steps on, and a host thread waits for that copy and runs write(host), which throws on failure.
+int start_job(const ShimState& S, const std::string& who, const double* dev, size_t n,
+              std::function<void(const double*)> write) {
   if (!io.drain) {
     if (hipStreamCreateWithFlags(&io.drain, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&io.packed, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&io.landed, hipEventDisableTiming) != hipSuccess) {
-      *S.err = "roms_gpu_wrt: stream/event creation failed";
+      *S.err = who + ": stream/event creation failed";
       return -2;
     }
   }
-  if (io.stage_n < n) {
-    if (io.stage) (void)hipFree(io.stage);
-    io.stage = nullptr;
-    if (hipMalloc(&io.stage, n * sizeof(double)) != hipSuccess) { *S.err = "roms_gpu_wrt: staging allocation failed"; return -2; }
-    io.stage_n = n;
-  }
-  if (io.pinned_n < n) {
+  const size_t need = n < 1 ? 1 : n;
+  if (io.pinned_n < need) {
     if (io.pinned) (void)hipHostFree(io.pinned);
     io.pinned = nullptr;
-    if (hipHostMalloc(&io.pinned, n * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-      *S.err = "roms_gpu_wrt: pinned staging allocation failed";
+    io.pinned_n = 0;
+    if (hipHostMalloc(&io.pinned, need * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      *S.err = who + ": pinned staging allocation failed";
       return -2;
     }
-    io.pinned_n = n;
-  }
-  // device snapshot on the library stream (ordered before the next step) ...
-  for (const OutVar& o : vars) {
-    const long m = (long)o.slab.ni * o.slab.nj * o.slab.nk;
-    hipLaunchKernelGGL(k_io_pack, dim3(blocks_for(m)), dim3(256), 0, S.s, o.slab, io.stage + o.off);
+    io.pinned_n = need;
   }
   if (hipEventRecord(io.packed, S.s) != hipSuccess || hipStreamWaitEvent(io.drain, io.packed, 0) != hipSuccess ||
-      hipMemcpyAsync(io.pinned, io.stage, n * sizeof(double), hipMemcpyDeviceToHost, io.drain) != hipSuccess ||
+      (n && hipMemcpyAsync(io.pinned, dev, n * sizeof(double), hipMemcpyDeviceToHost, io.drain) != hipSuccess) ||
       hipEventRecord(io.landed, io.drain) != hipSuccess) {
-    *S.err = "roms_gpu_wrt: snapshot enqueue failed";
+    *S.err = who + ": snapshot enqueue failed";
     return -2;
   }
-  if (hipGetLastError() != hipSuccess) { *S.err = "roms_gpu_wrt: pack launch failed"; return -3; }
-  // ... drained and written by a host thread while the model steps on
-  const std::string fpath(path);
-  const roms_tlev tl = *t;
-  const bool create = rec == 1;
-  nc::File* proto = new nc::File();
-  if (create) define_file(*proto, S, vars, rst, avg, period, zv, tv, uv);
-  const std::vector<double> depths = zv && create ? zv->vecdep : std::vector<double>();
-  if (avg) avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
-  if (tv) tdiag_window_written();   // diagnostics.F:778
-  if (uv) uvdiag_window_written();
   io.job.status = 0;
   io.job.err.clear();
   io.job.running = true;
@@ -474,48 +300,100 @@ int write_record(const char* path, int rec, int total_rec, double time, const ro
   const double* host = io.pinned;
   IoJob* job = &io.job;   // io is thread_local: the writer reports through this pointer
   io.job.th = std::thread([=]() {
-    std::unique_ptr<nc::File> f(proto);
     try {
       if (hipEventSynchronize(landed) != hipSuccess) throw std::runtime_error("snapshot copy failed");
-      if (create) f->create(fpath);
-      else f->open(fpath, true);
-      const int64_t r0 = rec - 1;
-      const int vt = f->find_var("ocean_time"), vs = f->find_var("time_step");
-      if (vt < 0 || vs < 0) throw std::runtime_error(fpath + ": not a file of this writer (no ocean_time/time_step)");
-      f->put_double(vt, r0, &time);
-      const int ts[6] = {tl.iic, rec, total_rec, 0, 0, 0};   // write_time_step (basic_output.F:1120-1150)
-      f->put_int(vs, r0, ts);
-      if (!depths.empty()) f->put_double(f->find_var("depth"), 0, depths.data());
-      for (const OutVar& o : vars) {
-        const int id = f->find_var(o.name);
-        if (id < 0) throw std::runtime_error(fpath + ": variable " + o.name + " not defined");
-        if (f->vars[id].count() != (int64_t)o.slab.ni * o.slab.nj * o.slab.nk)
-          throw std::runtime_error(fpath + ": variable " + o.name + " has another shape");
-        f->put_double(id, r0, host + o.off);
-      }
-      f->close();
+      write(host);
     } catch (const std::exception& e) {
       job->status = -7;
-      job->err = std::string("roms_gpu_wrt: ") + e.what();
+      job->err = who + ": " + e.what();
     }
   });
   return 0;
 }
 
+bool bad_record_args(const ShimState& S, const char* path, int rec, const roms_tlev* t) {
+  if (path && rec >= 1 && t) return false;
+  *S.err = "roms_gpu_wrt: bad path/record/time levels";
+  return true;
+}
+
 }  // namespace
 
-int zslice_write(const char* path, int rec, int total_rec, double time, const roms_tlev* t, const ZslView& zv) {
-  return write_record(path, rec, total_rec, time, t, false, 0, false, 0.0, &zv);
+// tracer names (tracers.F:296-301: temp, salt with SALINITY; passive tracers
+// get trcNN unless the host named them with roms_gpu_io_tracer_name)
+void io_tracer_meta(const ShimState& S, std::vector<std::string>& nm, std::vector<std::string>& un,
+                    std::vector<std::string>& ln) {
+  const int NT = S.d->b.NT;
+  const bool salinity = S.cfg->salinity != 0;
+  nm.assign(NT, ""); un.assign(NT, ""); ln.assign(NT, "");
+  for (int q = 0; q < NT; q++) {
+    if ((size_t)q < io.tname.size() && !io.tname[q].empty()) {
+      nm[q] = io.tname[q]; un[q] = io.tunits[q]; ln[q] = io.tlname[q];
+    } else if (q == 0) {
+      nm[q] = "temp"; un[q] = "Celsius"; ln[q] = "potential temperature";
+    } else if (q == 1 && salinity) {
+      nm[q] = "salt"; un[q] = "PSU"; ln[q] = "salinity";
+    } else {
+      char b[32];
+      snprintf(b, sizeof b, "trc%02d", q + 1);
+      nm[q] = b; un[q] = "nondim"; ln[q] = std::string("passive tracer ") + b;
+    }
+  }
 }
 
-int tdiag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
-                const TdiaView& tv) {
-  return write_record(path, rec, total_rec, time, t, false, 0, false, period, nullptr, &tv);
+OutVar out_var(const ShimState& S, const std::string& name, const std::string& long_name, const std::string& units,
+               char grid, int levels, int depth, const double* base, long level_stride) {
+  OutVar o;
+  o.name = name; o.lname = long_name; o.units = units; o.grid = grid; o.levels = levels; o.depth = depth;
+  o.slab = slab_of(S.d->b, part_of(*S.dims), base, grid, depth ? depth : levels ? levels : 1, level_stride);
+  return o;
 }
 
-int diag_write(const char* path, int rec, int total_rec, double time, double period, const roms_tlev* t,
-               const UvdView& uv, const TdiaView* tv) {
-  return write_record(path, rec, total_rec, time, t, false, 0, false, period, nullptr, tv, &uv);
+int write_record(const ShimState& S, const char* path, int rec, int total_rec, const roms_tlev* t, RecordSpec spec) {
+  if (bad_record_args(S, path, rec, t)) return -1;
+  int r = io_join(*S.err);
+  if (r) return r;
+  const std::string who = spec.who;
+  size_t n = 0;
+  for (OutVar& o : spec.vars) { o.off = (long)n; n += (size_t)o.slab.ni * o.slab.nj * o.slab.nk; }
+  if (io.stage_n < n) {
+    if (io.stage) (void)hipFree(io.stage);
+    io.stage = nullptr;
+    io.stage_n = 0;
+    if (hipMalloc(&io.stage, n * sizeof(double)) != hipSuccess) { *S.err = who + ": staging allocation failed"; return -2; }
+    io.stage_n = n;
+  }
+  // device snapshot on the library stream (ordered before the next step) ...
+  for (const OutVar& o : spec.vars) {
+    const long m = (long)o.slab.ni * o.slab.nj * o.slab.nk;
+    hipLaunchKernelGGL(k_io_pack, dim3(blocks_for(m)), dim3(256), 0, S.s, o.slab, io.stage + o.off);
+  }
+  if (hipGetLastError() != hipSuccess) { *S.err = who + ": pack launch failed"; return -3; }
+  // ... drained and written by a host thread while the model steps on
+  const std::string fpath(path);
+  const roms_tlev tl = *t;
+  const bool create = rec == 1;
+  std::shared_ptr<nc::File> f = std::make_shared<nc::File>();
+  if (create) define_file(*f, S, spec);
+  return start_job(S, who, io.stage, n, [=](const double* host) {
+    if (create) f->create(fpath);
+    else f->open(fpath, true);
+    const int64_t r0 = rec - 1;
+    const int vt = f->find_var("ocean_time"), vs = f->find_var("time_step");
+    if (vt < 0 || vs < 0) throw std::runtime_error(fpath + ": not a file of this writer (no ocean_time/time_step)");
+    f->put_double(vt, r0, &spec.time);
+    const int ts[6] = {tl.iic, rec, total_rec, 0, 0, 0};   // write_time_step (basic_output.F:1120-1150)
+    f->put_int(vs, r0, ts);
+    if (create && !spec.depths.empty()) f->put_double(f->find_var("depth"), 0, spec.depths.data());
+    for (const OutVar& o : spec.vars) {
+      const int id = f->find_var(o.name);
+      if (id < 0) throw std::runtime_error(fpath + ": variable " + o.name + " not defined");
+      if (f->vars[id].count() != (int64_t)o.slab.ni * o.slab.nj * o.slab.nk)
+        throw std::runtime_error(fpath + ": variable " + o.name + " has another shape");
+      f->put_double(id, r0, host + o.off);
+    }
+    f->close();
+  });
 }
 
 int io_writer_join(std::string& err) { return io_join(err); }
@@ -531,83 +409,44 @@ int extract_write(const char* path, int rec, double time, const ExtRecord& R) {
   int r = shim_enter(S, true);
   if (r) return r;
   if ((r = io_join(*S.err))) return r;
-  const size_t n = R.n < 1 ? 1 : R.n;
-  if (!io.drain) {
-    if (hipStreamCreateWithFlags(&io.drain, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&io.packed, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&io.landed, hipEventDisableTiming) != hipSuccess) {
-      *S.err = "roms_gpu_wrt_extract: stream/event creation failed";
-      return -2;
-    }
-  }
-  if (io.pinned_n < n) {
-    if (io.pinned) (void)hipHostFree(io.pinned);
-    io.pinned = nullptr;
-    io.pinned_n = 0;
-    if (hipHostMalloc(&io.pinned, n * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-      *S.err = "roms_gpu_wrt_extract: pinned staging allocation failed";
-      return -2;
-    }
-    io.pinned_n = n;
-  }
-  if (hipEventRecord(io.packed, S.s) != hipSuccess || hipStreamWaitEvent(io.drain, io.packed, 0) != hipSuccess ||
-      (R.n && hipMemcpyAsync(io.pinned, R.dev, R.n * sizeof(double), hipMemcpyDeviceToHost, io.drain) != hipSuccess) ||
-      hipEventRecord(io.landed, io.drain) != hipSuccess) {
-    *S.err = "roms_gpu_wrt_extract: snapshot enqueue failed";
-    return -2;
-  }
   const std::string fpath(path);
   const bool create = rec == 1;
-  nc::File* proto = new nc::File();
+  std::shared_ptr<nc::File> f = std::make_shared<nc::File>();
   if (create) {
-    const int dtm = proto->add_dim(R.time_dim, 0);
-    global_atts(*proto, S, "ROMS extraction file");
+    const int dtm = f->add_dim(R.time_dim, 0);
+    global_atts(*f, S, "ROMS extraction file");
     for (const std::string& tv : R.time_vars)
-      proto->add_var(tv, nc::NC_DOUBLE, {dtm}, {nc::Att::str("long_name", "Time since 2000"), nc::Att::str("units", "second")});
+      f->add_var(tv, nc::NC_DOUBLE, {dtm}, {nc::Att::str("long_name", "Time since 2000"), nc::Att::str("units", "second")});
     std::vector<int> dnp;
-    for (const auto& d : R.dims) dnp.push_back(proto->add_dim(d.first, d.second));
-    const int dz = R.s_rho > 0 ? proto->add_dim("s_rho", R.s_rho) : -1;
+    for (const auto& d : R.dims) dnp.push_back(f->add_dim(d.first, d.second));
+    const int dz = R.s_rho > 0 ? f->add_dim("s_rho", R.s_rho) : -1;
     for (const ExtFileVar& v : R.vars) {
       std::vector<int> dims{dtm};
       if (v.levels) dims.push_back(dz);
       dims.push_back(dnp[v.dim_np]);
-      proto->add_var(v.name, nc::NC_DOUBLE, dims,
-                     {nc::Att::i("start", {v.start}), nc::Att::i("count", {v.count}), nc::Att::str("dname", v.dname),
-                      nc::Att::i("dsize", {v.dsize}), nc::Att::str("long_name", v.lname), nc::Att::str("units", v.units)});
+      f->add_var(v.name, nc::NC_DOUBLE, dims,
+                 {nc::Att::i("start", {v.start}), nc::Att::i("count", {v.count}), nc::Att::str("dname", v.dname),
+                  nc::Att::i("dsize", {v.dsize}), nc::Att::str("long_name", v.lname), nc::Att::str("units", v.units)});
     }
   }
   const ExtRecord rc = R;
-  io.job.status = 0;
-  io.job.err.clear();
-  io.job.running = true;
-  hipEvent_t landed = io.landed;
-  const double* host = io.pinned;
-  IoJob* job = &io.job;
-  io.job.th = std::thread([=]() {
-    std::unique_ptr<nc::File> f(proto);
-    try {
-      if (hipEventSynchronize(landed) != hipSuccess) throw std::runtime_error("snapshot copy failed");
-      if (create) f->create(fpath);
-      else f->open(fpath, true);
-      const int64_t r0 = rec - 1;
-      for (const std::string& tv : rc.time_vars) {
-        const int id = f->find_var(tv);
-        if (id < 0) throw std::runtime_error(fpath + ": not an extraction file of these objects (no " + tv + ")");
-        f->put_double(id, r0, &time);
-      }
-      for (const ExtFileVar& v : rc.vars) {
-        const int id = f->find_var(v.name);
-        if (id < 0) throw std::runtime_error(fpath + ": variable " + v.name + " not defined");
-        if (f->vars[id].count() != (int64_t)v.n) throw std::runtime_error(fpath + ": variable " + v.name + " has another shape");
-        f->put_double(id, r0, host + v.off);
-      }
-      f->close();
-    } catch (const std::exception& e) {
-      job->status = -7;
-      job->err = std::string("roms_gpu_wrt_extract: ") + e.what();
+  return start_job(S, "roms_gpu_wrt_extract", R.dev, R.n, [=](const double* host) {
+    if (create) f->create(fpath);
+    else f->open(fpath, true);
+    const int64_t r0 = rec - 1;
+    for (const std::string& tv : rc.time_vars) {
+      const int id = f->find_var(tv);
+      if (id < 0) throw std::runtime_error(fpath + ": not an extraction file of these objects (no " + tv + ")");
+      f->put_double(id, r0, &time);
     }
+    for (const ExtFileVar& v : rc.vars) {
+      const int id = f->find_var(v.name);
+      if (id < 0) throw std::runtime_error(fpath + ": variable " + v.name + " not defined");
+      if (f->vars[id].count() != (int64_t)v.n) throw std::runtime_error(fpath + ": variable " + v.name + " has another shape");
+      f->put_double(id, r0, host + v.off);
+    }
+    f->close();
   });
-  return 0;
 }
 }  // namespace roms
 
@@ -616,13 +455,49 @@ using namespace roms;
 extern "C" {
 
 int roms_gpu_wrt_rst(const char* path, int rec, int total_rec, double time, const roms_tlev* t) {
-  return write_record(path, rec, total_rec, time, t, true, 0);
+  ShimState S;
+  int r = shim_enter(S, true);
+  if (r) return r;
+  if (bad_record_args(S, path, rec, t)) return -1;
+  RecordSpec spec;
+  spec.type = "ROMS restart file";
+  spec.time = time;
+  spec.vars = record_vars(S, *t, true, 0);
+  return write_record(S, path, rec, total_rec, t, spec);
 }
 int roms_gpu_wrt_his(const char* path, int rec, int total_rec, double time, const roms_tlev* t, int wrt_mask) {
-  return write_record(path, rec, total_rec, time, t, false, wrt_mask);
+  ShimState S;
+  int r = shim_enter(S, true);
+  if (r) return r;
+  if (bad_record_args(S, path, rec, t)) return -1;
+  const double* wvl = nullptr;
+  if (wrt_mask & ROMS_WRT_W) {   // call wvlcty (0, work), basic_output.F:390
+    if (t->nstp < 1 || t->nstp > 3) { *S.err = "roms_gpu_wrt_his: bad time levels"; return -1; }
+    wvl = wvl_compute(S, t->nstp, &r);
+    if (r) return r;
+  }
+  RecordSpec spec;
+  spec.type = "ROMS history file";
+  spec.time = time;
+  spec.vars = record_vars(S, *t, false, wrt_mask, nullptr, wvl);
+  return write_record(S, path, rec, total_rec, t, spec);
 }
+// wrt_avg_ocean_vars: the open window's means, ocean_time = their mean time
 int roms_gpu_wrt_avg(const char* path, int rec, int total_rec, double period, const roms_tlev* t) {
-  return write_record(path, rec, total_rec, 0.0, t, false, 0, true, period);
+  ShimState S;
+  int r = shim_enter(S, true);
+  if (r) return r;
+  if (bad_record_args(S, path, rec, t)) return -1;
+  const AvgView& av = avg_view();
+  RecordSpec spec;
+  if (!av.mask) { *S.err = "roms_gpu_wrt_avg: averaging is not armed (roms_gpu_avg_begin)"; return -4; }
+  if (!avg_window(&spec.time).have) { *S.err = "roms_gpu_wrt_avg: no sample in the window (roms_gpu_calc_avg)"; return -4; }
+  spec.type = "ROMS averages file";
+  spec.gatts.push_back({"averaging_timescale", seconds_att(period)});   // the window length (basic_output.F:451-455, 705)
+  spec.vars = record_vars(S, *t, false, av.mask, &av);
+  if ((r = write_record(S, path, rec, total_rec, t, spec))) return r;
+  avg_window_written();   // navg = 0: the next sample has coef == 1 (basic_output.F:501)
+  return 0;
 }
 int roms_gpu_io_wait(void) {
   std::string err;
@@ -788,7 +663,7 @@ int roms_gpu_get_init(const char* path, int req_rec, int tindx, roms_tlev* t, do
     upload(buf, F.v + (long)(tindx - 1) * b.n3, 'v', N, sk);
     exch(F.v + (long)(tindx - 1) * b.n3, N);
     std::vector<std::string> nm, un, ln;
-    tracer_meta(b.NT, S.cfg->salinity != 0, nm, un, ln);
+    io_tracer_meta(S, nm, un, ln);
     const int nts = S.cfg->salinity ? 2 : 1;
     for (int q = 0; q < b.NT; q++) {
       double* base = F.t + (long)(tindx - 1) * b.n3 + (long)q * 3 * b.n3;
