@@ -58,12 +58,14 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 31 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 32 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
   integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
                                ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
                                ROMS_WRT_AKT = 512, ROMS_WRT_AKS = 1024, ROMS_WRT_HBLS = 2048, ROMS_WRT_HBBL = 4096, &
                                ROMS_WRT_W = 8192, ROMS_WRT_DEFAULT = 63
+  ! roms_gpu_part_begin flags (ROMS_PART_*): the cell ordering of sort_particles after every call
+  integer(c_int), parameter :: ROMS_PART_SORT = 1
   ! extraction variables (ROMS_EXT_*); UP, VP, W, BGC are parsed and reported, not produced
   integer(c_int), parameter :: ROMS_EXT_ZETA = 1, ROMS_EXT_UBAR = 2, ROMS_EXT_VBAR = 4, ROMS_EXT_U = 8, &
                                ROMS_EXT_V = 16, ROMS_EXT_TEMP = 32, ROMS_EXT_SALT = 64, ROMS_EXT_UP = 128, &
@@ -332,6 +334,45 @@ module roms_gpu_mod
       integer(c_long), value :: count
     end function
     integer(c_int) function roms_gpu_time_wvlcty(n, t, ms) bind(c)
+      import :: c_int, c_double, roms_tlev
+      integer(c_int), value :: n
+      type(roms_tlev), intent(in) :: t
+      real(c_double), intent(out) :: ms(2)
+    end function
+    ! Lagrangian particles (k_particles.hip): do_particles of particles.F
+    integer(c_int) function roms_gpu_part_begin(npmx, fac_x, fac_y, fac_c, flags) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_long), value :: npmx
+      real(c_double), value :: fac_x, fac_y, fac_c
+      integer(c_int), value :: flags
+    end function
+    integer(c_int) function roms_gpu_part_add(n, px, py, pz, zmode) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_long), value :: n
+      real(c_double), intent(in) :: px(*), py(*), pz(*)
+      integer(c_int), value :: zmode
+    end function
+    integer(c_int) function roms_gpu_do_particles(t) bind(c)
+      import :: c_int, roms_tlev
+      type(roms_tlev), intent(in) :: t
+    end function
+    integer(c_int) function roms_gpu_part_state(out) bind(c)
+      import :: c_int, c_long
+      integer(c_long), intent(out) :: out(8)
+    end function
+    integer(c_int) function roms_gpu_part_copy_out(dst, count, global) bind(c)
+      import :: c_int, c_long, c_double
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+      integer(c_int), value :: global
+    end function
+    integer(c_int) function roms_gpu_wrt_part(path, rec, total_rec, time) bind(c)
+      import :: c_int, c_char, c_double
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int), value :: rec, total_rec
+      real(c_double), value :: time
+    end function
+    integer(c_int) function roms_gpu_time_do_particles(n, t, ms) bind(c)
       import :: c_int, c_double, roms_tlev
       integer(c_int), value :: n
       type(roms_tlev), intent(in) :: t

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 31
+#define ROMS_GPU_ABI_VERSION 32
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -638,6 +638,59 @@ int roms_gpu_time_calc_avg(int n, const roms_tlev *t, double *ms);
 int roms_gpu_wvlcty(const roms_tlev *t);
 int roms_gpu_wvlcty_copy_out(double *dst, long count);
 int roms_gpu_time_wvlcty(int n, const roms_tlev *t, double *ms);
+/* ---- Lagrangian particles on the device (ABI 32): do_particles of particles.F.
+ * Particles live in this rank's index space [0,Lm] x [0,Mm] x [0,N]: px = 0 is
+ * the western u face i = 1, rho point i sits at px = i - 0.5, rho level k at
+ * pz = k - 0.5.  The list is the reference's part(npmx, 13), column-major:
+ * tag, px py pz, pu pv pw (m/s), the index-space increments prx pry prz and
+ * their previous values.  The step never advances particles by itself.
+ * roms_gpu_part_begin allocates the list, its double buffer and the eight send
+ * and receive messages of fac_x, fac_y, fac_c * npmx * 13 words (N/S, E/W,
+ * corners; init_arrays_mpi_roms; 0: 0.1, 0.1, 0.01) and re-arms from empty;
+ * every rank of a run passes the same npmx and factors.  ROMS_PART_SORT: every
+ * call ends with sort_particles' ordering by floor(px) + floor(py)*Lm +
+ * floor(pz)*Lm*Mm (stable); without it the list keeps arrival order.
+ * roms_gpu_part_add appends n particles at (px, py, pz): zmode 0, pz in index
+ * space; zmode 1, pz a depth in metres (negative down) converted against z_w
+ * of the particle's column by zlev2kidx's formula and clamped into [0, N].
+ * Tags are ip + 10000000*mynode and go on from the rank's ntag.  Particles
+ * added before the first roms_gpu_do_particles take part in its dm = d start,
+ * later ones start from dm = 0 (seed_bry).  It fails and changes nothing if
+ * the list would exceed npmx or a position lies outside the index space.
+ * roms_gpu_do_particles, called after a step (main.F:501), on the library
+ * stream: rhs_particles (trilinear u, v(t->nnew), Wp, Hz, bilinear pm, pn with
+ * their halos as the step left them) and advance_particles (AB2, bottom and
+ * surface clamps), exchange_particles (eight neighbours through the rank's
+ * communicator; a periodic direction of one rank wraps; an edge without a
+ * neighbour loses the particle), removal of the dead, arrivals appended in the
+ * order sw, s, se, w, e, nw, n, ne, then the ordering if armed.  Compaction and
+ * packing are stable, so list and messages are the same from run to run.  Wp,
+ * which the reference allocates and never fills, is ((We+Wi)*pm)*pn.  Where
+ * the reference stops -- a particle more than half a cell outside the rank, a
+ * full message -- the device reads nothing out of range, gives the particle
+ * zero increments (n_range) or keeps what fits (n_overflow), and every later
+ * roms_gpu_do_particles / roms_gpu_wrt_part returns -5 until re-armed.  Each
+ * call reads one block of counters back (one stream synchronisation).
+ * roms_gpu_part_state: np, ntag, n_sur, n_bot, n_lost (died at an edge without
+ * a neighbour), n_moved (sent or wrapped), n_range, n_overflow.
+ * roms_gpu_part_copy_out: the live list as part(np, 13), column-major; count
+ * must be at least np*13; global != 0: px, py + iSW_corn + 0.5, jSW_corn + 0.5.
+ * roms_gpu_wrt_part: record rec (1 creates the file) of the _part file through
+ * the writer thread: particles(time, seven, npart = npmx), double, long_name
+ * 'Tag/x/y/z/u/v/w', px and py global, rows past np zero (tags start at 1);
+ * ocean_time; global attribute big_number = 10000000.  total_rec is accepted
+ * for symmetry with the other writers and not stored.
+ * roms_gpu_time_do_particles: n calls on a copy of the list between events on
+ * the library stream, total milliseconds: ms[0] whole calls, ms[1] the rhs and
+ * advance kernel alone.  The particles do not move.                        */
+#define ROMS_PART_SORT 1
+int roms_gpu_part_begin(long npmx, double fac_x, double fac_y, double fac_c, int flags);
+int roms_gpu_part_add(long n, const double *px, const double *py, const double *pz, int zmode);
+int roms_gpu_do_particles(const roms_tlev *t);
+int roms_gpu_part_state(long out[8]);
+int roms_gpu_part_copy_out(double *dst, long count, int global);
+int roms_gpu_wrt_part(const char *path, int rec, int total_rec, double time);
+int roms_gpu_time_do_particles(int n, const roms_tlev *t, double ms[2]);
 /* ---- tracer budget terms on the device (ABI 30): DIAGNOSTICS with diag_trc,
  * diagnostics.F and its hooks in step3d_t_ISO.F, the non-isoneutral build.
  * For every armed tracer six terms of the corrector step3d_t, each N planes in

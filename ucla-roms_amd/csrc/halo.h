@@ -121,6 +121,16 @@ void halo_free(Halo& H);
 bool halo_graph_safe(const Halo* H);
 long halo_map(const HaloPlan& P, int dir, int unpack, int* iv, int* jv);
 void halo_exchange(const Halo& H, hipStream_t s, const ExchList& L);
+// Fixed-length messages to the plan's neighbours beside the field exchanges (the particle lists of k_particles.hip):
+// sb[d], len[d] doubles, goes to the neighbour in direction d and arrives there as rb[opp(d)]; len[d] is the same on
+// both sides (0: no message).  Blocking; uses none of the exchanges' buffers, plans or counters.  Over RCCL one
+// send / receive group, between threads of one process device copies, over the host channel the host's allgather.
+struct MsgSet {
+  double* sb[8];
+  double* rb[8];
+  long len[8];
+};
+int halo_exchange_messages(const Halo& H, hipStream_t s, const MsgSet& M);
 // exchange L on H.cs after the work already queued on s (fork), returns its
 // ticket; halo_join makes s wait for every forked exchange, halo_join_to for
 // ticket t and those before it (no-ops for exchanges already joined)

@@ -194,6 +194,7 @@ struct LocalGroup {
   long gen = 0;
   std::vector<double*> sbuf;
   std::vector<std::vector<double>> red;
+  std::vector<MsgSet> msg;   // halo_exchange_messages: every rank's message set of the call in flight
   long cap = 0;
   void barrier() {
     std::unique_lock<std::mutex> lk(m);
@@ -257,6 +258,7 @@ RomsComm* comm_create_local(int group, int nranks, int rank) {
     gp->n = nranks;
     gp->sbuf.assign(nranks, nullptr);
     gp->red.assign(nranks, {});
+    gp->msg.assign(nranks, MsgSet{});
   }
   return new RomsComm{2, rank, nranks, nullptr, gp, 0, nullptr, nullptr};
 }
@@ -774,6 +776,66 @@ void halo_exchange(const Halo& H, hipStream_t s, const ExchList& L) {
   ktimer_mark(s, kTimedHaloUnpack, 0);
   hipLaunchKernelGGL(k_halo_unpack, grid, dim3(256), 0, s, g, L, H.rbuf, H.cap);
   ktimer_mark(s, kTimedHaloUnpack, 1, 1);
+}
+
+int halo_exchange_messages(const Halo& H, hipStream_t s, const MsgSet& M) {
+  RomsComm* c = H.comm;
+  const HaloGeom& g = H.plan.g;
+  if (!c) return -1;
+  const int me = c->rank;
+  auto on = [&](int d) { return g.active[d] && M.len[d] > 0; };
+  if (c->kind == 1) {
+    (void)ncclGroupStart();
+    for (int d = 0; d < 8; d++)
+      if (on(d) && (H.plan.peer[d] != me || c->route_self))
+        (void)ncclSend(M.sb[d], (size_t)M.len[d], ncclDouble, H.plan.peer[d], c->nccl, s);
+    // as in halo_exchange: receive opp(d) in the order the peer sent direction d
+    for (int d = 0; d < 8; d++) {
+      const int h = kOpp[d];
+      if (on(h) && (H.plan.peer[h] != me || c->route_self))
+        (void)ncclRecv(M.rb[h], (size_t)M.len[h], ncclDouble, H.plan.peer[h], c->nccl, s);
+    }
+    (void)ncclGroupEnd();
+    for (int h = 0; h < 8; h++)
+      if (on(h) && H.plan.peer[h] == me && !c->route_self)
+        (void)hipMemcpyAsync(M.rb[h], M.sb[kOpp[h]], (size_t)M.len[h] * sizeof(double), hipMemcpyDeviceToDevice, s);
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : -2;
+  }
+  if (c->kind == 3) {
+    // every rank's eight messages in one block of the host's allgather, scattered from the neighbours' blocks
+    long off[9] = {0};
+    for (int d = 0; d < 8; d++) off[d + 1] = off[d] + M.len[d];
+    double tot = (double)off[8];
+    std::vector<double> sizes((size_t)c->nranks);
+    if (halo_allgather(H, s, &tot, 1, sizes.data()) != 0) return -3;
+    for (double v : sizes)
+      if (v != tot) return -4;   // the ranks must arm lists of one size
+    std::vector<double> mine((size_t)(off[8] > 0 ? off[8] : 1), 0.0), all((size_t)(off[8] > 0 ? off[8] : 1) * c->nranks);
+    for (int d = 0; d < 8; d++)
+      if (on(d) && copy_on(mine.data() + off[d], M.sb[d], (size_t)M.len[d] * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return -2;
+    if (hipStreamSynchronize(s) != hipSuccess) return -2;
+    if (c->hfn(c->hctx, mine.data(), (long)(mine.size() * sizeof(double)), all.data()) != 0) return -3;
+    for (int h = 0; h < 8; h++)
+      if (on(h) && copy_on(M.rb[h], all.data() + (size_t)H.plan.peer[h] * mine.size() + off[kOpp[h]],
+                           (size_t)M.len[h] * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
+        return -2;
+    return 0;
+  }
+  LocalGroup* G = c->grp;
+  {
+    std::lock_guard<std::mutex> lk(G->m);
+    G->msg[me] = M;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return -2;
+  G->barrier();
+  for (int h = 0; h < 8; h++)
+    if (on(h))
+      (void)hipMemcpyAsync(M.rb[h], G->msg[H.plan.peer[h]].sb[kOpp[h]], (size_t)M.len[h] * sizeof(double),
+                           hipMemcpyDeviceToDevice, s);
+  const hipError_t e = hipStreamSynchronize(s);
+  G->barrier();
+  return e == hipSuccess ? 0 : -2;
 }
 
 long halo_fork_exchange(Halo& H, hipStream_t s, const ExchList& L) {

@@ -428,6 +428,7 @@ void free_all() {
   uvdiag_free();
   zslice_free();
   extract_free();
+  part_free();
   frc_free();
   if (g.small) { (void)hipFree(g.small); g.small = nullptr; g.small_n = 0; }
   if (g.stage) { (void)hipFree(g.stage); g.stage = nullptr; g.stage_n = 0; }

@@ -23,7 +23,8 @@
 // basic_output.F:421-515: the running means of k_avg.hip in place of the
 // fields) here, slices (zslice_output.F:284-410) in k_zslice.hip, the budget
 // terms in k_tdiag.hip and k_uvdiag.hip.  The extraction file defines itself
-// (extract_write) and shares start_job, the drain and the writer thread.
+// (extract_write) and shares start_job, the drain and the writer thread; so
+// does the particles file (part_write, k_particles.hip's record).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -445,6 +446,37 @@ int extract_write(const char* path, int rec, double time, const ExtRecord& R) {
       if (f->vars[id].count() != (int64_t)v.n) throw std::runtime_error(fpath + ": variable " + v.name + " has another shape");
       f->put_double(id, r0, host + v.off);
     }
+    f->close();
+  });
+}
+
+// One record of the particles file (create_particles_file / wrt_particles, particles.F:389-473): create_file's
+// time dimension, ocean_time and global attributes, then particles(time, seven, npart) -- the reference's
+// (npart = npmx, seven, time) read in C order -- with its long_name, and the global attribute big_number.
+int part_write(const ShimState& S, const char* path, int rec, double time, const double* dev, long npmx, int big_number) {
+  int r = io_join(*S.err);
+  if (r) return r;
+  const std::string fpath(path);
+  const bool create = rec == 1;
+  std::shared_ptr<nc::File> f = std::make_shared<nc::File>();
+  if (create) {
+    const int dtm = f->add_dim("time", 0);
+    f->add_var("ocean_time", nc::NC_DOUBLE, {dtm},
+               {nc::Att::str("long_name", "Time since 2000/01/01"), nc::Att::str("units", "second")});
+    global_atts(*f, S, "ROMS particles file");
+    const int dnp = f->add_dim("npart", npmx), d7 = f->add_dim("seven", 7);
+    f->add_var("particles", nc::NC_DOUBLE, {dtm, d7, dnp}, {nc::Att::str("long_name", "Tag/x/y/z/u/v/w")});
+    f->gatts.push_back(nc::Att::i("big_number", {big_number}));
+  }
+  const size_t n = (size_t)npmx * 7;
+  return start_job(S, "roms_gpu_wrt_part", dev, n, [=](const double* host) {
+    if (create) f->create(fpath);
+    else f->open(fpath, true);
+    const int vt = f->find_var("ocean_time"), vp = f->find_var("particles");
+    if (vt < 0 || vp < 0) throw std::runtime_error(fpath + ": not a particles file (no ocean_time/particles)");
+    if (f->vars[vp].count() != (int64_t)n) throw std::runtime_error(fpath + ": particles has another npart");
+    f->put_double(vt, rec - 1, &time);
+    f->put_double(vp, rec - 1, host);
     f->close();
   });
 }

@@ -1,5 +1,5 @@
 // shim_state.h -- what the C-ABI modules outside roms_shim.cpp (rst_io.hip and
-// the output producers k_avg, k_zslice, k_extract, k_wvlcty, k_tdiag, k_uvdiag)
+// the output producers k_avg, k_zslice, k_extract, k_wvlcty, k_tdiag, k_uvdiag, k_particles)
 // share: the calling thread's library state, the record description a producer
 // hands the writer, the event timer of the roms_gpu_time_* entries, and the
 // few calls the producers make into one another.
@@ -181,6 +181,10 @@ struct ExtRecord {
 };
 int extract_write(const char* path, int rec, double time, const ExtRecord& R);
 int io_writer_join(std::string& err);   // joins the writer thread (0 or its error)
+// Lagrangian particles (k_particles.hip): one record of the _part file for rst_io.hip's writer thread (its npart
+// and seven dimensions do not fit OutVar).  dev: particles(npart, seven) packed on the library stream
+int part_write(const ShimState& S, const char* path, int rec, double time, const double* dev, long npmx, int big_number);
+void part_free();                       // roms_gpu_finalize
 void extract_free();                    // roms_gpu_finalize
 void shim_extract_huv(bool on);         // whole steps store Hz_u/Hz_v while an armed object reads them
 bool shim_hzuv_valid();                 // the stored Hz_u/Hz_v are set_HUV's of the last step

@@ -150,6 +150,13 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_wvlcty.argtypes = [P(Tlev)]
     L.roms_gpu_wvlcty_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_long]
     L.roms_gpu_time_wvlcty.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_part_begin.argtypes = [ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int]
+    L.roms_gpu_part_add.argtypes = [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    L.roms_gpu_do_particles.argtypes = [P(Tlev)]
+    L.roms_gpu_part_state.argtypes = [P(ctypes.c_long)]
+    L.roms_gpu_part_copy_out.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_int]
+    L.roms_gpu_wrt_part.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    L.roms_gpu_time_do_particles.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
     L.roms_gpu_tdiag_begin.argtypes = [ctypes.c_int, P(ctypes.c_int), ctypes.c_int]
     L.roms_gpu_tdiag_sample.argtypes = [ctypes.c_int]
     L.roms_gpu_tdiag_state.argtypes = [P(ctypes.c_int)] * 4
@@ -253,6 +260,12 @@ WRT_ALL = 16383
 AVG_FIELDS = dict(zeta=(1, 0), ubar=(2, 0), vbar=(4, 0), u=(8, 1), v=(16, 1), t=(32, 1), temp=(32, 1), salt=(32, 1),
                   rho=(64, 1), omega=(128, 2), Akv=(256, 2), Akt=(512, 2), Aks=(1024, 2), hbls=(2048, 0),
                   hbbl=(4096, 0), w=(8192, 1))
+# Lagrangian particles (particles.F): words of a particle, ROMS_PART_SORT, the tag offset per rank
+PART_NPV = 13
+PART_WORDS = ("tag", "px", "py", "pz", "pu", "pv", "pw", "prx", "pry", "prz", "prxm", "prym", "przm")
+PART_SORT = 1
+PART_BIG_NUMBER = 10000000
+PART_STATE = ("np", "ntag", "n_sur", "n_bot", "n_lost", "n_moved", "n_range", "n_overflow")
 # ROMS_ZSL_* of include/roms_gpu.h (zslice_output.opt wrt_*_zsl switches)
 ZSL_T, ZSL_U, ZSL_V = 1, 2, 4
 ZSL_MAXDEP = 32
@@ -381,6 +394,28 @@ class FileAllgather:
 def comm_destroy(h):
     load_library().roms_gpu_comm_destroy(h)
     _host_channels.pop(getattr(h, "value", h), None)
+
+
+def part_full_seed(model, ppm3, rng):
+    """The full_seed branch of init_particles with seed_particles (particles.F:146-163, 358-387) on the host:
+    floor(h/(pm*pn)*ppm3) particles in every column of the rank, columns in the order j then i, uniform in the
+    cell and uniform in depth between z_w(0) and z_w(N) (depths ascending within a column, as zlev2kidx leaves
+    them), drawn from the numpy Generator `rng` and handed to part_add with zmode 1.  Returns their number."""
+    nx, ny = model.Lm, model.Mm
+    inner = (slice(2, ny + 2), slice(2, nx + 2))
+    h, pm, pn = (model.get(k)[0][inner] for k in ("h", "pm", "pn"))
+    zw = model.get("z_w")
+    lnp = np.floor(h / (pm * pn) * ppm3).astype(np.int64).ravel()
+    lnp[lnp < 0] = 0
+    col = np.repeat(np.arange(nx * ny), lnp)
+    n = col.size
+    z0, z1 = zw[0][inner].ravel()[col], zw[-1][inner].ravel()[col]
+    z = rng.random(n) * (z1 - z0) + z0
+    order = np.lexsort((z, col))
+    px = rng.random(n) + (col % nx)
+    py = rng.random(n) + (col // nx)
+    model.part_add(px, py, z[order], zmode=1)
+    return n
 
 
 class Model:
@@ -802,6 +837,49 @@ class Model:
         """(ms of n store launches, ms of n running-mean launches; the latter 0 unless W is armed)."""
         ms = (ctypes.c_double * 2)()
         self._chk(self.L.roms_gpu_time_wvlcty(n, ctypes.byref(self.t), ms), "time_wvlcty")
+        return ms[0], ms[1]
+
+    # ---- Lagrangian particles (do_particles, particles.F) ----
+    def part_begin(self, npmx, fac_x=0.0, fac_y=0.0, fac_c=0.0, sort=False):
+        """Arm an empty list of at most npmx particles; the factors size the messages to the N/S, E/W and corner
+        neighbours as fractions of npmx (0: the reference's 0.1, 0.1, 0.01).  sort: every do_particles ends with
+        sort_particles' cell ordering (off by default: profiles/part_cost.txt)."""
+        self._chk(self.L.roms_gpu_part_begin(npmx, fac_x, fac_y, fac_c, PART_SORT if sort else 0), "part_begin")
+
+    def part_add(self, px, py, pz, zmode=0):
+        """Append particles at index-space positions (px, py) and pz: an index-space level (zmode 0) or a depth in
+        metres, negative down (zmode 1)."""
+        a = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (px, py, pz)]
+        if not a[0].size == a[1].size == a[2].size:
+            raise ValueError("part_add: px, py and pz differ in length")
+        self._chk(self.L.roms_gpu_part_add(a[0].size, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, zmode),
+                  "part_add")
+
+    def do_particles(self):
+        """One call of do_particles after a step (main.F:501): rhs, advance, exchange, removal of the dead."""
+        self._chk(self.L.roms_gpu_do_particles(ctypes.byref(self.t)), "do_particles")
+
+    def part_state(self):
+        """dict of np, ntag, n_sur, n_bot, n_lost, n_moved, n_range, n_overflow."""
+        out = (ctypes.c_long * 8)()
+        self._chk(self.L.roms_gpu_part_state(out), "part_state")
+        return dict(zip(PART_STATE, out))
+
+    def particles(self, global_=False):
+        """The live list as an (np, 13) array (PART_WORDS); global_: px, py as the file holds them."""
+        n = self.part_state()["np"]
+        a = np.empty((PART_NPV, n), dtype=np.float64)
+        self._chk(self.L.roms_gpu_part_copy_out(a.ctypes.data, a.size, int(global_)), "part_copy_out")
+        return np.ascontiguousarray(a.T)
+
+    def wrt_part(self, path, rec, total_rec, time):
+        """wrt_particles: record rec of this rank's particles file."""
+        self._chk(self.L.roms_gpu_wrt_part(path.encode(), rec, total_rec, time), "wrt_part")
+
+    def time_do_particles(self, n):
+        """(ms of n whole calls, ms of n launches of the rhs and advance kernel), on a copy of the list."""
+        ms = (ctypes.c_double * 2)()
+        self._chk(self.L.roms_gpu_time_do_particles(n, ctypes.byref(self.t), ms), "time_do_particles")
         return ms[0], ms[1]
 
     # ---- tracer budget terms (DIAGNOSTICS with diag_trc, diagnostics.F) ----
