@@ -48,6 +48,7 @@ program register_driver
   do id = 0, ROMS_NFIELDS - 1
     nel = roms_gpu_field_size(id)
     allocate(f(id)%a(nel))
+    if (nel == 0) cycle   ! a field this configuration does not have (the ADV_ISONEUTRAL arrays): nothing to transfer
     call roms_gpu_check(roms_gpu_copy_out(id, c_loc(f(id)%a), nel), 'copy_out')
   end do
   call put(ROMS_zeta, zeta); call put(ROMS_ubar, ubar); call put(ROMS_vbar, vbar)
@@ -72,6 +73,7 @@ program register_driver
 
   ! 3. register the host arrays (module-shaped where the reference has them), upload
   do id = 0, ROMS_NFIELDS - 1
+    if (roms_gpu_field_size(id) == 0) cycle
     select case (id)
     case (ROMS_zeta);  call reg(id, c_loc(zeta), size(zeta, kind=c_long))
     case (ROMS_ubar);  call reg(id, c_loc(ubar), size(ubar, kind=c_long))

@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 32 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 33 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
   integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
                                ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
@@ -82,7 +82,10 @@ module roms_gpu_mod
   ! field ids (enum roms_field) used by the drivers below
   integer(c_int), parameter :: ROMS_ALL = -1
   integer(c_int), parameter :: ROMS_zeta = 22, ROMS_ubar = 23, ROMS_vbar = 24, ROMS_u = 25, ROMS_v = 26, &
-                               ROMS_t = 27, ROMS_Hz = 32, ROMS_z_r = 35, ROMS_NFIELDS = 105
+                               ROMS_t = 27, ROMS_Hz = 32, ROMS_z_r = 35, ROMS_NFIELDS = 111
+  ! ADV_ISONEUTRAL arrays (size 0 and every transfer refused without the switch)
+  integer(c_int), parameter :: ROMS_dRdx = 105, ROMS_dRde = 106, ROMS_idRz = 107, ROMS_diff3u = 108, &
+                               ROMS_diff3v = 109, ROMS_Akz = 110
 
   interface
     integer(c_int) function roms_gpu_abi_version() bind(c)

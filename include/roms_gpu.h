@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 32
+#define ROMS_GPU_ABI_VERSION 33
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -138,6 +138,11 @@ enum roms_field {
      [degC], specific humidity Q [kg/kg], precipitation [cm/day], short-wave (the data read into
      srflx) and downward long-wave radiation [W/m2]; and the rho-point stresses sustr_r, svstr_r */
   ROMS_uwnd, ROMS_vwnd, ROMS_tair, ROMS_qair, ROMS_prate, ROMS_swrad, ROMS_lwrad, ROMS_sustr_r, ROMS_svstr_r,
+  /* ADV_ISONEUTRAL (eos_vars.F:28-31, mixing.F:24-27): the slopes dRdx, dRde (N) of the corrector prsgrd, the
+     limited inverse stratification idRz (0:N) and the roots of the hyperdiffusivities diff3u, diff3v (N) of
+     step3d_uv2, and step3d_t's stabilising diffusivity Akz (0:N), a private scratch array of the reference.
+     They exist with roms_cfg.adv_isoneutral only: otherwise their size is 0 and every transfer of them fails. */
+  ROMS_dRdx, ROMS_dRde, ROMS_idRz, ROMS_diff3u, ROMS_diff3v, ROMS_Akz,
   ROMS_NFIELDS
 };
 

@@ -6,9 +6,10 @@ cpu_baseline leg may import this package.  Parity pinned against the
 reference golden log tests/Filament/benchmark.result_github_gnu; the
 open-boundary routines, set_nudgcof and the bulk fluxes against the reference
 routines themselves, compiled by oracle/ref/build_ref.sh (oracle.ref,
-tests/test_ref_pin_obc.py, tests/test_ref_pin_bulk.py).  Still unpinned: the
-CURVGRID momentum terms, tides and forcing interpolation, ADV_ISONEUTRAL,
-LMD_DDMIX.
+tests/test_ref_pin_obc.py, tests/test_ref_pin_bulk.py), and ADV_ISONEUTRAL
+against prsgrd, step3d_uv2 and step3d_t compiled with the switch
+(tests/test_ref_pin_iso.py).  Still unpinned: the CURVGRID momentum terms,
+tides and forcing interpolation, LMD_DDMIX.
 """
 import ctypes
 import os

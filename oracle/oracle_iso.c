@@ -14,17 +14,25 @@
  *                gradient, w-levels 1..N-1)
  * exchanged like the reference (step3d_uv1.F:529-532, step3d_uv2.F:730-732).
  *
- * Parity: no reference case with input data in /root/reference enables
- * ADV_ISONEUTRAL (tests/Flux_frc needs input_data that is not checked in),
- * so this restatement is parity unpinned to reference output; it is the
- * checker for the HIP path (tests/test_iso.py).
+ * Parity: pinned bit for bit to the reference's own prsgrd.F, step3d_uv2.F and
+ * step3d_t_ISO.F, which oracle/ref/build_ref.sh compiles unchanged with
+ * ADV_ISONEUTRAL (libraries iso0, iso6, iso9, iso15, isoper) and
+ * tests/test_ref_pin_iso.py runs beside this restatement on a state that takes
+ * every arm (branch_states.iso_state): dRdx, dRde; diff3u, diff3v, idRz, u, v,
+ * ubar, vbar, FlxU, FlxV; t and Akz, whole arrays, ghost rows included.
  *
  * One deviation, forced by the reference reading unset scratch: at a
  * physical (non-periodic) edge prsgrd's dRdx(istr) reads rx(istr-1) and
  * dRdx(iend+1) reads rx(iend+2), two cells its extrapolation never writes
  * (prsgrd.F:256-268 sets only rx(imin-1), rx(imax+1)); the same for dRde at
  * the south/north edges.  The restatement continues the extrapolation
- * (rx(imin-2) = rx(imin), rx(imax+2) = rx(imax)), like k_iso.hip.
+ * (rx(imin-2) = rx(imin), rx(imax+2) = rx(imax)), like k_iso.hip.  The pin
+ * finds the undefined cells by running the reference with its scratch filled
+ * with two different values: they are exactly dRdx(istr, jstr:jend, :),
+ * dRdx(iend+1, jstr:jend, :), dRde(istr:iend, jstr, :), dRde(istr:iend,
+ * jend+1, :) on non-periodic edges, none on periodic ones, and no output of
+ * step3d_uv2 or step3d_t (Akz, a scratch array of the reference, is written
+ * on the interior at the w-levels 1..N-1 only).
  */
 #include "oracle_core.h"
 

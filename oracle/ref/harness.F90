@@ -10,6 +10,11 @@
 ! the ghost points the modules hold them in, which is also the layout
 ! of the oracle (oracle/roms_oracle.h).
 
+! the switch sets without boundary forcing (the periodic library) have no ubind and no v_sponge
+#if defined T_FRC_BRY || defined M2_FRC_BRY || defined M3_FRC_BRY || defined Z_FRC_BRY
+# define HAVE_UBIND
+#endif
+
 module ref_harness
   use iso_c_binding, only: c_int, c_double
   implicit none
@@ -37,7 +42,13 @@ contains
                      west_exchng, east_exchng, south_exchng, north_exchng
     use hidden_mpi_vars, only: inode, jnode, west_msg_exch, east_msg_exch, south_msg_exch, north_msg_exch
     use dimensions, only: init_dimensions
-    use scalars, only: init, visc2, tnu2, Akv_bak, Akt_bak, rho0, gamma2, v_sponge, ubind
+    use scalars, only: init, visc2, tnu2, Akv_bak, Akt_bak, rho0, gamma2
+#ifdef SPONGE
+    use scalars, only: v_sponge
+#endif
+#ifdef HAVE_UBIND
+    use scalars, only: ubind
+#endif
     use ocean_vars, only: init_arrays_ocean
     use private_scratch, only: init_arrays_private_scratch
     use grid, only: init_arrays_grid
@@ -53,7 +64,13 @@ contains
     west_exchng = .false.; east_exchng = .false.; south_exchng = .false.; north_exchng = .false.
     west_msg_exch = .false.; east_msg_exch = .false.; south_msg_exch = .false.; north_msg_exch = .false.
     init = 0.0d0; visc2 = 0.0d0; tnu2 = 0.0d0; Akv_bak = 0.0d0; Akt_bak = 0.0d0
-    rho0 = 1000.0d0; gamma2 = 1.0d0; v_sponge = 0.0d0; ubind = 0.0d0
+    rho0 = 1000.0d0; gamma2 = 1.0d0
+#ifdef SPONGE
+    v_sponge = 0.0d0
+#endif
+#ifdef HAVE_UBIND
+    ubind = 0.0d0
+#endif
     call init_dimensions
     call init_arrays_ocean
     call init_arrays_private_scratch
@@ -83,13 +100,19 @@ contains
 
   ! iv: kstp knew nstp nrhs nnew ub_tune;  dv: dt dtfast ubind gamma2 rho0
   subroutine ref_set_scalars(iv, dv) bind(C, name="ref_set_scalars")
-    use scalars, only: kstp, knew, nstp, nrhs, nnew, dt, dtfast, ubind, gamma2, rho0
+    use scalars, only: kstp, knew, nstp, nrhs, nnew, dt, dtfast, gamma2, rho0
+#ifdef HAVE_UBIND
+    use scalars, only: ubind
+#endif
     use sponge_tune, only: ub_tune
     integer(c_int), intent(in) :: iv(6)
     real(c_double), intent(in) :: dv(5)
     kstp = iv(1); knew = iv(2); nstp = iv(3); nrhs = iv(4); nnew = iv(5)
     ub_tune = iv(6) /= 0
-    dt = dv(1); dtfast = dv(2); ubind = dv(3); gamma2 = dv(4); rho0 = dv(5)
+    dt = dv(1); dtfast = dv(2); gamma2 = dv(4); rho0 = dv(5)
+#ifdef HAVE_UBIND
+    ubind = dv(3)
+#endif
   end subroutine ref_set_scalars
 
   subroutine ref_set_ocean(a_zeta, a_ubar, a_vbar, a_u, a_v, a_t) bind(C, name="ref_set_ocean")
@@ -188,6 +211,7 @@ contains
     call t3dbc_tile(istr, iend, jstr, jend, it, scratch)
   end subroutine ref_t3dbc
 
+#ifdef SPONGE
   ! init_arrays_mixing sets visc2_r = visc2_p = visc2 and diff2 = tnu2,
   ! set_nudgcof adds the sponge bands
   subroutine ref_set_nudgcof(a_vsponge, a_visc2, a_tnu2, o_visc2_r, o_visc2_p, o_diff2) bind(C, name="ref_set_nudgcof")
@@ -213,6 +237,7 @@ contains
     o_visc2_p(1:size(visc2_p)) = reshape(visc2_p, [size(visc2_p)])
     o_diff2(1:size(diff2)) = reshape(diff2, [size(diff2)])
   end subroutine ref_set_nudgcof
+#endif
 
   ! atmosphere in; t, u, v, the masks, nrhs and rho0 as set before.  The
   ! flux arrays go in and out: the routine leaves some ghost points, and

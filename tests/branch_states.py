@@ -543,3 +543,261 @@ def bulk_arms(o, cfg, tix):
             "wspd > 3 (current feedback)": wspd > 3.0, "wspd <= 3": wspd <= 3.0,
             "rain": f("prate") > 0.0, "no rain": f("prate") == 0.0, "wet": wet, "land": ~wet,
             "ice: t < -1.8": wet & (sst < T_ICE), "ice: t = -1.8": wet & (sst == T_ICE), "no ice": wet & (sst > T_ICE)}
+
+
+# ------------------------------------------------------------------- ISO ----
+ISO_SIZE = dict(LLm=24, MMm=20, N=6)         # the grid of the reference libraries (oracle/ref/build_ref.sh)
+ISO_ARRAYS = ("dRdx", "dRde", "idRz", "diff3u", "diff3v", "Akz")
+ISO_LMD = 7                                   # LMD_MIXING + LMD_KPP + LMD_BKPP: idRz's hbls / hbbl arms, no ghat
+ISO_SHARE = 0.01                              # every arm on at least this share of the points it is evaluated on
+QP2 = 0.0000172                               # eos_vars.F:25
+ISO_EPSIL = 1.0e-33                           # step3d_uv2.F:73
+ISO_SQUEEZE = 3.2                             # columns squeezed down to exp(-3.2) = 4 % of their depth
+
+
+def iso_cfg(obc, LLm, MMm, N, NT=2):
+    """ADV_ISONEUTRAL on the closed or open basin (split EOS, KPP and BKPP without the non-local term,
+    curvilinear terms on), or for obc = 'per' on the doubly periodic Filament (linear EOS, no LMD)."""
+    if obc == "per":
+        c = oracle.filament_cfg(LLm=LLm, MMm=MMm, N=N, NT=NT, sizex=200.0 * LLm, sizey=50.0 * MMm, np_xi=1, np_eta=1)
+        c.adv_isoneutral = 1
+        return c
+    from test_iso import iso_cfg as basin
+    c = basin(LLm=LLm, MMm=MMm, N=N, lmd=ISO_LMD, obc=obc)
+    c.NT, c.salinity, c.curvgrid = NT, int(NT > 1), 1
+    return c
+
+
+def iso_land(LLm, MMm, per=False):
+    """On every edge one land cell (with its ghost neighbour between walls) and one beside it, a row or a
+    column further in: (i, j) in Fortran indices."""
+    jw, je, js, jn = MMm // 3, MMm // 2 + 1, LLm // 3 + 1, 2 * LLm // 3 - 1
+    on = [(1, jw), (LLm, je), (js, 1), (jn, MMm)]
+    ghost = [] if per else [(0, jw), (LLm + 1, je), (js, 0), (jn, MMm + 1)]
+    beside = [(2, 2 * MMm // 3), (LLm - 1, MMm // 4), (2 * LLm // 3 + 1, 2), (LLm // 5 + 1, MMm - 1)]
+    return on + ghost + beside
+
+
+def _wrap_all(a, per):
+    import metrics
+    if per[0] or per[1]:
+        for plane in a:
+            metrics.wrap(plane, per)
+
+
+def build_iso(obc, LLm=ISO_SIZE["LLm"], MMm=ISO_SIZE["MMm"], N=ISO_SIZE["N"], NT=2):
+    """(cfg, oracle, corrector's time indices, snapshot) for the open sides obc, or obc = 'per'.  The ISO basin
+    (the Filament for 'per') on the metric sweep's rough planes after three steps, then, from a fixed seed:
+      * every column squeezed by a smooth factor between 1 and exp(-ISO_SQUEEZE) (z_r, z_w, Hz and the fluxes
+        through them), so that z_r slopes under every face and the bottom and top cells fall on both sides of
+        the 50 m of idRz's blending;
+      * noise on rho1 and qp1 (rho) of the size of the vertical density differences: slopes of both signs at
+        every corner of a triad, dRz below zero on part of the points, either side of the limiter winning;
+      * hbls and hbbl between 5 m and 1 km; noise on t, u, v, with t(nnew) = Hz*t and u, v(nnew) = Hz*u, Hz*v
+        as pre_step3d and step3d_uv1 leave them;
+      * land on and beside every edge (iso_land);
+      * one water point at the centre with f = 0 on the points around it and rho1, qp1 (rho) uniform over the
+        5 x 5 columns around it: flat and unstratified, so that epsil wins idRz's limiter there;
+      * one water point a quarter of the way in with rho1 (rho) uniform along the levels of the 5 x 5 columns
+        around it and growing upwards: flat and unstable, so that max(dRz, 0.) decides the limiter there
+        (elsewhere dRx_max outweighs the rotational term that is left of a clamped dRz).
+    The snapshot holds every field; it is never written, callers restore the oracle from it."""
+    import metrics
+    per = obc == "per"
+    assert LLm >= 12 and MMm >= 12 and N >= 2
+    cfg = iso_cfg(obc, LLm, MMm, N, NT)
+    o = oracle.Oracle(cfg)
+    o.init()
+    metrics.apply_grid(o, None, (metrics.periodic_rough if per else metrics.rough)(LLm, MMm))
+    o.step(3)
+    tix = set_mode(o, "corr")
+    nstp, nnew = tix[3], tix[5]
+    o.L.or_rho_eos(o.h, 3)
+    rng = np.random.default_rng(700 + (16 if per else obc))
+    pp = (bool(cfg.ew_periodic), bool(cfg.ns_periodic))
+    f = lambda n: o.field(n)
+    # squeeze the columns
+    i, j = np.arange(-1.0, LLm + 3)[None, :], np.arange(-1.0, MMm + 3)[:, None]
+    w = (0.5 + 0.5 * np.sin(2.0 * np.pi * (i - 0.5) / LLm + 0.4)) * (0.5 + 0.5 * np.cos(2.0 * np.pi * (j - 0.5) / MMm + 1.1))
+    s = np.exp(-ISO_SQUEEZE * w / w.max())
+    su, sv = s.copy(), s.copy()
+    su[:, 1:] = 0.5 * (s[:, 1:] + s[:, :-1])
+    sv[1:, :] = 0.5 * (s[1:, :] + s[:-1, :])
+    for names, fac in ((("z_r", "z_w", "Hz", "We", "Wi"), s), (("FlxU", "Hz_u", "DU_avg1", "DU_avg2"), su),
+                       (("FlxV", "Hz_v", "DV_avg1", "DV_avg2"), sv)):
+        for n in names:
+            f(n)[...] *= fac
+    # density
+    for n in (("rho1", "qp1") if cfg.nonlin_eos else ("rho",)):
+        a = f(n)
+        amp = max(float(np.median(np.abs(a[1:] - a[:-1]))), 1e-3 * float(np.abs(a).max()), 1e-6)
+        a += 0.7 * amp * rng.standard_normal(a.shape)
+    # boundary layers
+    for n in ("hbls", "hbbl"):
+        f(n)[...] = 10.0 ** rng.uniform(0.7, 3.0, f(n).shape)
+    # tracers and velocities
+    t = f("t").reshape(cfg.NT, 3, N, MMm + 4, LLm + 4)
+    for q in range(cfg.NT):
+        t[q] += 0.1 * max(float(np.abs(t[q]).max()), 0.05) * rng.standard_normal(t[q].shape)
+        t[q, nnew - 1] = f("Hz") * t[q, nstp - 1]
+    for n, hz in (("u", "Hz_u"), ("v", "Hz_v")):
+        a = f(n).reshape(3, N, MMm + 4, LLm + 4)
+        a += max(float(np.abs(a).max()), 0.05) * rng.standard_normal(a.shape)
+        a[nnew - 1] *= f(hz)
+    # land
+    rm = f("rmask")[0]
+    for (li, lj) in iso_land(LLm, MMm, per):
+        rm[lj + 1, li + 1] = 0.0
+    metrics.wrap(rm, pp)
+    um, vm, pm_ = f("umask")[0], f("vmask")[0], f("pmask")[0]
+    um[:, 1:] = rm[:, 1:] * rm[:, :-1]
+    vm[1:, :] = rm[1:, :] * rm[:-1, :]
+    pm_[1:, 1:] = rm[1:, 1:] * rm[1:, :-1] * rm[:-1, 1:] * rm[:-1, :-1]
+    for m in (um, vm, pm_):
+        metrics.wrap(m, pp)
+    for n, m in (("zeta", rm), ("ubar", um), ("vbar", vm), ("u", um), ("v", vm), ("t", rm)):
+        f(n)[...] *= m
+    # the flat, unstratified point
+    ic, jc = iso_flat_point(LLm, MMm)
+    f("f")[0][jc:jc + 3, ic:ic + 3] = 0.0
+    for n in (("rho1", "qp1") if cfg.nonlin_eos else ("rho",)):
+        f(n)[:, jc - 1:jc + 4, ic - 1:ic + 4] = f(n)[N - 1, jc + 1, ic + 1]
+    assert rm[jc - 1:jc + 4, ic - 1:ic + 4].min() == 1.0
+    # the flat, unstably stratified point: f as it is, density uniform along the levels and growing upwards
+    iu, ju = iso_unstable_point(LLm, MMm)
+    for n in (("rho1", "qp1") if cfg.nonlin_eos else ("rho",)):
+        col = f(n)[N - 1, ju + 1, iu + 1] + (0.3 * np.arange(N) if n != "qp1" else np.zeros(N))
+        f(n)[:, ju - 1:ju + 4, iu - 1:iu + 4] = col[:, None, None]
+    assert rm[ju - 1:ju + 4, iu - 1:iu + 4].min() == 1.0 and abs(f("f")[0][ju + 1, iu + 1]) > 0.0
+    import romsgpu as rg
+    names = [n for n in rg.FIELDS + rg.ISO_FIELDS if _has_field(o, n)]
+    for n in names:
+        _wrap_all(f(n), pp) if f(n).ndim == 3 else None
+    snap = {n: f(n).copy() for n in names}
+    for a in snap.values():
+        a.setflags(write=False)
+    return cfg, o, tix, snap
+
+
+def _has_field(o, n):
+    try:
+        o.field(n)
+        return True
+    except KeyError:
+        return False
+
+
+def iso_flat_point(LLm, MMm):
+    """(i, j) of the flat, unstratified water point."""
+    return LLm // 2, MMm // 2
+
+
+def iso_unstable_point(LLm, MMm):
+    """(i, j) of the flat, unstably stratified water point."""
+    return LLm // 4, MMm // 2
+
+
+iso_state = functools.lru_cache(maxsize=None)(build_iso)      # one oracle per case, shared: restore before use
+
+
+def iso_restore(o, snap, tix):
+    for n, a in snap.items():
+        o.field(n)[...] = a
+    o.set_tindex(tix)
+
+
+def _at(a, di=0, dj=0):
+    """a(i+di, j+dj) on the layout of a."""
+    return np.roll(a, (-dj, -di), axis=(-2, -1))
+
+
+def iso_limiter_arms(S):
+    """The data-dependent arms of step3d_uv2.F:622-697 from its inputs (S: the arrays handed to the routine under
+    their names, and cfg), on the interior at the w-levels 1..N-1: the clamp of dRz, which of cff*dRz, dRx_max
+    and epsil wins the limiter, and the min / max arms of the blending factors cfs and cfb."""
+    cfg = S["cfg"]
+    N, I = cfg.N, box(cfg)
+    zr, zw, fc = S["z_r"], S["z_w"], S["f"][0]
+    r0g = cfg.rho0 / G
+    if cfg.nonlin_eos:
+        dpth = -0.5 * (zr[1:] + zr[:-1])
+        raw = S["rho1"][:-1] - S["rho1"][1:] + (S["qp1"][:-1] - S["qp1"][1:]) * dpth * (1. - 2. * QP2 * dpth)
+    else:
+        raw = S["rho"][:-1] - S["rho"][1:]
+    dRz = np.maximum(raw, 0.) + r0g * (fc * fc) * (zr[1:] - zr[:-1])
+    aX, aE = np.abs(S["dRdx"]), np.abs(S["dRde"])
+    mx = S["dm_u"][0] * np.maximum(aX[:-1], aX[1:])
+    me = S["dn_v"][0] * np.maximum(aE[:-1], aE[1:])
+    dRx_max = np.maximum(np.maximum(mx, _at(mx, 1, 0)), np.maximum(me, _at(me, 0, 1)))
+    arms = {}
+    if cfg.lmd:
+        hs, hb = S["hbls"][0], S["hbbl"][0]
+        ds, db = np.maximum(50., hs), np.maximum(50., hb)
+        arms.update({"hbls > 50 m": np.broadcast_to(hs > 50., raw.shape), "hbls < 50 m": np.broadcast_to(hs < 50., raw.shape),
+                     "hbbl > 50 m": np.broadcast_to(hb > 50., raw.shape), "hbbl < 50 m": np.broadcast_to(hb < 50., raw.shape)})
+    else:
+        ds = db = 50.
+    qs, qb = (zw[N] - zw[1:N]) / ds, (zw[1:N] - zw[0]) / db
+    cfs, cfb = np.minimum(1., qs), np.minimum(1., qb)
+    cff = 2. * cfs * (2. - cfs) * cfb * (2. - cfb)
+    a = cff * dRz
+    rot = r0g * (fc * fc) * (zr[1:] - zr[:-1])
+    arms.update({"dRz < 0 before its max(., 0)": raw < 0., "dRz > 0": raw > 0.,
+                 "limiter: cff*dRz": (a > dRx_max) & (a > ISO_EPSIL), "limiter: dRx_max": (dRx_max >= a) & (dRx_max > ISO_EPSIL),
+                 "point: epsil wins the limiter": (a <= ISO_EPSIL) & (dRx_max <= ISO_EPSIL),
+                 "point: max(dRz, 0.) decides the limiter": (raw < 0.) & (a > dRx_max) & (cff * (raw + rot) < dRx_max),
+                 "cfs < 1": qs < 1., "cfs = 1": qs >= 1., "cfb < 1": qb < 1., "cfb = 1": qb >= 1.})
+    return {k: v[I] for k, v in arms.items()}
+
+
+def iso_operator_arms(S):
+    """The data-dependent arms of step3d_t_ISO.F:411-485 and :656-695 from the five arrays it is handed, on the
+    interior between the levels k and k+1, k = 1..N-1: the eight sign tests of SW_TRIADS, the numbers idx and
+    ide of triads they select (0..4 each), and which of the four corners wins each of the four maxima of Akz."""
+    cfg = S["cfg"]
+    I = box(cfg)
+    X, E, d3u, d3v = S["dRdx"], S["dRde"], S["diff3u"], S["diff3v"]
+    lo, up = slice(0, -1), slice(1, None)
+    cx = {"dRdx(i,k) < 0": X[lo] < 0., "dRdx(i,k+1) > 0": X[up] > 0., "dRdx(i+1,k+1) < 0": _at(X, 1, 0)[up] < 0.,
+          "dRdx(i+1,k) > 0": _at(X, 1, 0)[lo] > 0.}
+    ce = {"dRde(j,k) < 0": E[lo] < 0., "dRde(j,k+1) > 0": E[up] > 0., "dRde(j+1,k+1) < 0": _at(E, 0, 1)[up] < 0.,
+          "dRde(j+1,k) > 0": _at(E, 0, 1)[lo] > 0.}
+    arms = {}
+    for c in (cx, ce):
+        for k, v in c.items():
+            arms[k], arms["not " + k] = v, ~v
+    idx, ide = sum(v.astype(int) for v in cx.values()), sum(v.astype(int) for v in ce.values())
+    for q in range(5):
+        arms["idx = %d" % q], arms["ide = %d" % q] = idx == q, ide == q
+    fsc = S["idRz"][1:-1] * (S["z_r"][1:] - S["z_r"][:-1])
+    sq = lambda a: (fsc * a) * (fsc * a)
+    Hz = S["Hz"]
+    with np.errstate(all="ignore"):       # Hz = 0 in ghost cells outside the interior
+        cff = 2. / (Hz[1:] + Hz[:-1])
+    cff2, cffX, cffE = cff * cff, S["pm"][0] * S["pm"][0], S["pn"][0] * S["pn"][0]
+    # corners in the order LL, RL, LU, RU (left / right, lower / upper)
+    ux = [(d3u[lo], sq(X[lo])), (_at(d3u, 1, 0)[lo], sq(_at(X, 1, 0)[lo])), (d3u[up], sq(X[up])),
+          (_at(d3u, 1, 0)[up], sq(_at(X, 1, 0)[up]))]
+    ve = [(d3v[lo], sq(E[lo])), (_at(d3v, 0, 1)[lo], sq(_at(E, 0, 1)[lo])), (d3v[up], sq(E[up])),
+          (_at(d3v, 0, 1)[up], sq(_at(E, 0, 1)[up]))]
+    with np.errstate(all="ignore"):
+        maxima = {"Akz max 1 (diff3u*s2)": [d * s2 for d, s2 in ux], "Akz max 2 (diff3v*s2)": [d * s2 for d, s2 in ve],
+                  "Akz max 3 (diff3u*(pm2 + cff2*s2))": [d * (cffX + cff2 * s2) for d, s2 in ux],
+                  "Akz max 4 (diff3v*(pn2 + cff2*s2))": [d * (cffE + cff2 * s2) for d, s2 in ve]}
+    for name, cand in maxima.items():
+        c = np.stack([x[I] for x in cand])
+        win, top = np.argmax(c, axis=0), c.max(axis=0)
+        for q, corner in enumerate(("LL", "RL", "LU", "RU")):
+            arms["%s: %s wins" % (name, corner)] = (win == q) & (top > 0.)
+    return {k: (v if k.startswith("Akz") else v[I]) for k, v in arms.items()}
+
+
+def iso_shares(arms, where, show=True):
+    """Assert ISO_SHARE of the points on every arm (one point for the arms named 'point: ..'); returns the shares."""
+    shares = {k: float(np.mean(v)) for k, v in arms.items()}
+    if show:
+        print("ISO arm shares %s: " % (where,) + ", ".join("%s %.3f" % kv for kv in shares.items()))
+    short = [(where, k, shares[k]) for k, v in arms.items()
+             if (not np.any(v) if k.startswith("point:") else shares[k] < ISO_SHARE)]
+    assert not short, short
+    return shares

@@ -69,7 +69,10 @@ def test_field_table_matches_header():
     body = src[src.index("enum roms_field"):src.index("ROMS_NFIELDS")]
     ids = re.findall(r"ROMS_(\w+)", body)
     ids = [i for i in ids if i != "ALL"]
-    assert ids == romsgpu.FIELDS
+    # the ADV_ISONEUTRAL arrays stand last and apart: what copies a whole state walks FIELDS alone
+    assert ids == romsgpu.FIELDS + romsgpu.ISO_FIELDS
+    assert [romsgpu.FIELD_ID[n] for n in ids] == list(range(len(ids)))
+    assert int(re.search(r"ROMS_NFIELDS = (\d+)", open(os.path.join(ROOT, "fortran", "roms_gpu_mod.F90")).read()).group(1)) == len(ids)
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libromsgpu.so not built")

@@ -131,7 +131,8 @@ def coast_model(cfg, size):
         m = romsgpu.Model.from_case(cfg.case_id, cfg.LLm, cfg.MMm, cfg.N, cfg.NT, salinity=bool(cfg.salinity),
                                     nonlin_eos=bool(cfg.nonlin_eos), dt=cfg.dt, ndtfast=cfg.ndtfast, sizex=cfg.sizex,
                                     sizey=cfg.sizey, lmd=cfg.lmd, surf_flux=bool(cfg.surf_flux), obc=cfg.obc,
-                                    v_sponge=cfg.v_sponge, curvgrid=bool(cfg.curvgrid), bulk_frc=bool(cfg.bulk_frc))
+                                    v_sponge=cfg.v_sponge, curvgrid=bool(cfg.curvgrid), bulk_frc=bool(cfg.bulk_frc),
+                                    adv_isoneutral=bool(cfg.adv_isoneutral))
     edges, strips, _ = SIZES[size]
     # prsgrd_takes_strips (k_prsgrd.hip:379): no strips on a curvilinear grid, the tiles run every row
     want = {"edges": 1 if cfg.obc else edges, "strips": None if cfg.curvgrid else strips, "omega_seg": True}

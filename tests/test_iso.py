@@ -4,8 +4,10 @@ slopes dRdx/dRde (prsgrd.F:307-338, 423-453) and step3d_uv2's diff3u/diff3v/
 idRz (step3d_uv2.F:572-697) -- in oracle/oracle_iso.c (two-slice recursive
 form, like the reference) and ucla-roms_amd/csrc/k_iso.hip (full 3-D fields).
 
-Parity is unpinned to reference output: the only reference case that defines
-ADV_ISONEUTRAL (tests/Flux_frc) reads input_data that is not checked in.  So:
+Parity is pinned: tests/test_ref_pin_iso.py holds the oracle's three routines
+to the reference's own, compiled with the switch (oracle/ref/build_ref.sh), bit
+for bit on a state that takes every arm, and tests/test_gpu_iso.py holds the
+kernels to both, stage by stage, at every size that switches a path.  Here:
   * CPU: the oracle's slope and limiter formulas against a numpy evaluation
     of the same Fortran expressions on the oracle's own state (interior cells
     away from the edges, where the reference reads unset scratch -- see
@@ -169,9 +171,9 @@ def test_gpu_iso_steps_match_oracle(kind):
     per-routine bound), then 20 steps within the north_star RMS bound,
     ADV_ISONEUTRAL on in both.  basin_obc6 and basin_obc9 open two sides only,
     so that every side runs the LapT edge copy and the zero of a closed edge,
-    and every corner lies between one of each.  These ISO edge copies remain
-    unpinned to the reference, as the rest of the operator (see above): the
-    oracle is the only yardstick for them."""
+    and the SW and NE corners lie between one of each.  The oracle's edge
+    copies are pinned to the reference's step3d_t for the same sets of open
+    sides (tests/test_ref_pin_iso.py, libraries iso0, iso6, iso9, iso15)."""
     from test_gpu_parity import PROGNOSTIC, RMS_RUN, check_fields
     cfg = _gpu_case(kind)
     o = oracle.Oracle(cfg)

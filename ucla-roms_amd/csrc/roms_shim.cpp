@@ -309,6 +309,9 @@ Bounds make_bounds(const roms_dims& D, int pitch, int gx = 0) {
 // boundary arrays and the vertical stretching curves are not (i,j) planes
 bool planar_field(int id) { return !(id == ROMS_Cs_w || id == ROMS_Cs_r || (id >= ROMS_zeta_west && id <= ROMS_t_north)); }
 
+// ADV_ISONEUTRAL's arrays: allocated with the switch only (roms_gpu_init), never by the loops over every field
+bool iso_field(int id) { return id >= ROMS_dRdx && id <= ROMS_Akz; }
+
 long field_count(int id, const Bounds& b) {
   const long n2 = b.n2, n3 = b.n3, n3w = b.n3w;
   switch (id) {
@@ -317,9 +320,10 @@ long field_count(int id, const Bounds& b) {
     case ROMS_u: case ROMS_v: return 3 * n3;
     case ROMS_t: return 3 * n3 * b.NT;
     case ROMS_FlxU: case ROMS_FlxV: case ROMS_Hz: case ROMS_Hz_u: case ROMS_Hz_v: case ROMS_z_r: case ROMS_rho:
-    case ROMS_rho1: case ROMS_qp1: case ROMS_ru: case ROMS_rv: return n3;
+    case ROMS_rho1: case ROMS_qp1: case ROMS_ru: case ROMS_rv: case ROMS_dRdx: case ROMS_dRde: case ROMS_diff3u:
+    case ROMS_diff3v: return n3;
     case ROMS_We: case ROMS_Wi: case ROMS_z_w: case ROMS_bvf: case ROMS_Akv: case ROMS_ghat: case ROMS_swr_frac:
-      return n3w;
+    case ROMS_idRz: case ROMS_Akz: return n3w;
     case ROMS_Akt: return n3w * b.nTS;
     case ROMS_diff2: case ROMS_stflx: return n2 * b.NT;
     default: break;
@@ -440,7 +444,10 @@ void free_all() {
   for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
   g.graphs.clear();
   for (int id = 0; id < ROMS_NFIELDS; id++)
-    if (g.f[id].d) { (void)hipFree(dev_base(g.f[id].d)); g.f[id] = FieldDesc{}; }
+    if (g.f[id].d) {
+      if (!iso_field(id)) (void)hipFree(dev_base(g.f[id].d));   // those are freed with g.scratch
+      g.f[id] = FieldDesc{};
+    }
   for (double* p : g.scratch) (void)hipFree(dev_base(p));
   g.guard_base.clear();
   if (g.arena) { (void)hipFree(g.arena); g.arena = nullptr; g.arena_n = g.arena_used = 0; }
@@ -1045,7 +1052,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     // set passes 2 GiB allocates them one by one (and runs the pointer form)
     long n = 11 * dev_alloc_size(b.n2);   // s0..s9, z_sd
     for (int id = 0; id < ROMS_NFIELDS; id++)
-      if (planar2d(id)) n += dev_alloc_size(field_count(id, b));
+      if (planar2d(id) && !iso_field(id)) n += dev_alloc_size(field_count(id, b));
     if (n * 8 < 2147483648L - (1L << 20)) {
       CHECK_HIP(hipMalloc(&g.arena, (size_t)n * sizeof(double)));
       g.arena_n = n;
@@ -1053,7 +1060,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     }
   }
   for (int id = 0; id < ROMS_NFIELDS; id++)
-    if (planar2d(id) && field(id)) return -2;
+    if (planar2d(id) && !iso_field(id) && field(id)) return -2;
   auto scratch = [&](double*& p, long n) -> int {
     CHECK_HIP(dev_alloc(p, n));
     g.scratch.push_back(p);
@@ -1066,7 +1073,7 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
   if (scratch(F.z_sd, b.n2)) return -2;
   g.arena_n = g.arena_used;   // nothing else is sliced from it
   for (int id = 0; id < ROMS_NFIELDS; id++)
-    if (!planar2d(id) && field(id)) return -2;
+    if (!planar2d(id) && !iso_field(id) && field(id)) return -2;
   if (scratch(F.P, b.n3) || scratch(F.rhos, b.n3) || scratch(F.c0, b.n3w) || scratch(F.c1, b.n3w) ||
       scratch(F.c2, b.n3w) || scratch(F.c3, b.n3w))
     return -2;
@@ -1100,6 +1107,16 @@ int roms_gpu_init(const roms_dims* dims, const roms_cfg* cfg, int device, void* 
     double** w3[] = {&F.idRz, &F.Akz, &F.iso_dTdz, &F.iso_FSC};
     for (double** q : w3)
       if (scratch(*q, b.n3w)) return -2;
+    // readable and writable through the field table (tests compare every intermediate of the operator)
+    const std::pair<int, double*> tab[] = {{ROMS_dRdx, F.dRdx}, {ROMS_dRde, F.dRde}, {ROMS_idRz, F.idRz},
+                                           {ROMS_diff3u, F.diff3u}, {ROMS_diff3v, F.diff3v}, {ROMS_Akz, F.Akz}};
+    for (const auto& e : tab) {
+      FieldDesc& d = g.f[e.first];
+      d.d = e.second;
+      d.count = field_count(e.first, b);
+      d.hcount = field_count(e.first, g.hb);
+      d.planar = true;
+    }
   }
   if (P.lmd) {
     if (scratch(F.lmd_rig, b.n3w)) return -2;
@@ -1168,6 +1185,7 @@ long roms_gpu_field_size(int id) {
 int roms_gpu_register(int id, double* host, long count) {
   REQUIRE_INIT();
   if (id < 0 || id >= ROMS_NFIELDS) { g.err = "roms_gpu_register: bad field id"; return -1; }
+  if (!g.f[id].d) { g.err = "roms_gpu_register: the field does not exist in this configuration (ADV_ISONEUTRAL is off)"; return -1; }
   if (count != g.f[id].hcount) { g.err = "roms_gpu_register: size mismatch for field"; return -1; }
   g.f[id].host = host;
   g.f[id].host_count = count;
@@ -1205,6 +1223,7 @@ int roms_gpu_download(int id) { REQUIRE_INIT_RO(); return xfer(id, false); }
 int roms_gpu_copy_in(int id, const double* src, long count) {
   REQUIRE_INIT();
   if (id < 0 || id >= ROMS_NFIELDS || count != g.f[id].hcount) { g.err = "roms_gpu_copy_in: bad field/size"; return -1; }
+  if (!g.f[id].d) { g.err = "roms_gpu_copy_in: the field does not exist in this configuration (ADV_ISONEUTRAL is off)"; return -1; }
   if (id == ROMS_Hz_u || id == ROMS_Hz_v) g.hzuv_valid = true;
   vg_host_write(id);
   CHECK_HIP(field_h2d(id, g.f[id].d, src));
@@ -1213,6 +1232,7 @@ int roms_gpu_copy_in(int id, const double* src, long count) {
 int roms_gpu_copy_out(int id, double* dst, long count) {
   REQUIRE_INIT_RO();
   if (id < 0 || id >= ROMS_NFIELDS || count != g.f[id].hcount) { g.err = "roms_gpu_copy_out: bad field/size"; return -1; }
+  if (!g.f[id].d) { g.err = "roms_gpu_copy_out: the field does not exist in this configuration (ADV_ISONEUTRAL is off)"; return -1; }
   if (!hzuv_readable(id)) return -5;
   if (id == ROMS_Akt) CHECK_HIP(akt_sync());
   CHECK_HIP(field_d2h(id, dst, g.f[id].d));

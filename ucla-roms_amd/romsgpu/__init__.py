@@ -26,7 +26,10 @@ FIELDS = ["h", "hinv", "f", "fomn", "pm", "pn", "dm_r", "dn_r", "dm_u", "dn_u", 
           "hbls", "hbbl", "ghat", "swr_frac", "sustr", "svstr", "stflx", "srflx", "swflx", "ru", "rv"] + \
          ["%s_%s" % (v, e) for v in ("zeta", "ubar", "vbar", "u", "v", "t") for e in ("west", "east", "south", "north")] + \
          ["dndx", "dmde", "ptide", "uwnd", "vwnd", "tair", "qair", "prate", "swrad", "lwrad", "sustr_r", "svstr_r"]
-FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
+# ADV_ISONEUTRAL's arrays (ROMS_dRdx .. ROMS_Akz), apart from FIELDS: what copies a whole state walks FIELDS, and
+# these exist with the switch only (size 0 and every get/put refused without it)
+ISO_FIELDS = ["dRdx", "dRde", "idRz", "diff3u", "diff3v", "Akz"]
+FIELD_ID = {n: i for i, n in enumerate(FIELDS + ISO_FIELDS)}
 CASE_FILAMENT, CASE_BASIN, CASE_PIPES, CASE_RIVERS = 0, 1, 2, 3
 # LMD switch bits (ROMS_LMD_* of include/roms_gpu.h)
 LMD_MIXING, LMD_KPP, LMD_BKPP, LMD_RIMIX, LMD_CONVEC, LMD_NONLOCAL = 1, 2, 4, 8, 16, 32
