@@ -58,7 +58,7 @@ module roms_gpu_mod
   ! LMD switch bits of lmd_mixing (ROMS_LMD_*)
   integer(c_int), parameter :: ROMS_LMD_MIXING = 1, ROMS_LMD_KPP = 2, ROMS_LMD_BKPP = 4, ROMS_LMD_RIMIX = 8, &
                                ROMS_LMD_CONVEC = 16, ROMS_LMD_NONLOCAL = 32, ROMS_LMD_DDMIX = 64
-  integer(c_int), parameter :: ROMS_GPU_ABI = 33 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
+  integer(c_int), parameter :: ROMS_GPU_ABI = 34 ! ROMS_GPU_ABI_VERSION, include/roms_gpu.h
   ! output switches of roms_gpu_wrt_his / roms_gpu_avg_begin (ROMS_WRT_*)
   integer(c_int), parameter :: ROMS_WRT_Z = 1, ROMS_WRT_UB = 2, ROMS_WRT_VB = 4, ROMS_WRT_U = 8, ROMS_WRT_V = 16, &
                                ROMS_WRT_T = 32, ROMS_WRT_R = 64, ROMS_WRT_O = 128, ROMS_WRT_AKV = 256, &
@@ -77,6 +77,9 @@ module roms_gpu_mod
   integer(c_int), parameter :: ROMS_UVD_U = 0, ROMS_UVD_V = 1
   integer(c_int), parameter :: ROMS_UVD_PGR = 1, ROMS_UVD_COR = 2, ROMS_UVD_ADV = 3, ROMS_UVD_DIS = 4, &
                                ROMS_UVD_HMX = 5, ROMS_UVD_VMX = 6, ROMS_UVD_CPL = 7, ROMS_UVD_PREV = 8
+  ! arrays of roms_gpu_pflx_copy_out / _copy_in (ROMS_PFLX_*, calc_pflx_mod.F:22-27)
+  integer(c_int), parameter :: ROMS_PFLX_UP = 1, ROMS_PFLX_VP = 2, ROMS_PFLX_U_SLOW = 3, ROMS_PFLX_V_SLOW = 4, &
+                               ROMS_PFLX_P_SLOW = 5
   integer(c_int), parameter :: ROMS_FRC_SURFACE = 1, ROMS_FRC_BRY = 2
 
   ! field ids (enum roms_field) used by the drivers below
@@ -445,6 +448,39 @@ module roms_gpu_mod
       integer(c_int), value :: n
       type(roms_tlev), intent(inout) :: t
       real(c_double), intent(out) :: ms(4)
+    end function
+    ! baroclinic pressure fluxes (k_pflx.hip): calc_pressure_flux of calc_pflx_mod.F after the corrector's prsgrd
+    integer(c_int) function roms_gpu_pflx_begin(timescale, on) bind(c)
+      import :: c_int, c_double
+      real(c_double), value :: timescale
+      integer(c_int), value :: on
+    end function
+    integer(c_int) function roms_gpu_pflx_state(armed, alpha, nsamples) bind(c)
+      import :: c_int, c_double, c_long
+      integer(c_int), intent(out) :: armed
+      real(c_double), intent(out) :: alpha
+      integer(c_long), intent(out) :: nsamples
+    end function
+    integer(c_int) function roms_gpu_pflx_path(formed, streamed) bind(c)
+      import :: c_int, c_long
+      integer(c_long), intent(out) :: formed, streamed
+    end function
+    integer(c_int) function roms_gpu_pflx_copy_out(which, dst, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: which
+      real(c_double), intent(out) :: dst(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_pflx_copy_in(which, src, count) bind(c)
+      import :: c_int, c_long, c_double
+      integer(c_int), value :: which
+      real(c_double), intent(in) :: src(*)
+      integer(c_long), value :: count
+    end function
+    integer(c_int) function roms_gpu_time_pflx(n, ms) bind(c)
+      import :: c_int, c_double
+      integer(c_int), value :: n
+      real(c_double), intent(out) :: ms(2)
     end function
     ! z-level slices (k_zslice.hip): calc_zslice / wrt_zslice of zslice_output.F
     integer(c_int) function roms_gpu_zslice_begin(what, ndep, vecdep, nt_z, trc2zsc, do_avg) bind(c)

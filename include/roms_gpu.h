@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ROMS_GPU_ABI_VERSION 33
+#define ROMS_GPU_ABI_VERSION 34
 #define ROMS_MAX_FAST 288
 
 /* Subdomain geometry of this rank: param.F / dimensions.F / mpi_setup.F:39-210 */
@@ -829,6 +829,69 @@ int roms_gpu_uvdiag_state(int *armed, int *do_avg, int *navg, int *sampling);
 int roms_gpu_uvdiag_copy_out(int comp, int term, double *dst, long count);
 int roms_gpu_wrt_diag(const char *path, int rec, int total_rec, double time, double period, const roms_tlev *t);
 int roms_gpu_time_uvdiag(int n, roms_tlev *t, double ms[4]);
+/* ---- baroclinic pressure fluxes on the device (ABI 34): calc_pressure_flux of
+ * calc_pflx_mod.F on the P of the corrector's prsgrd (prsgrd.F:160-226, 466-
+ * 468).  Off until roms_gpu_pflx_begin arms it; not armed, no routine launches
+ * or allocates anything more and whole steps are the graphs they were.
+ * roms_gpu_pflx_begin(timescale, on): on = 1 arms with alpha = dt/timescale,
+ * beta = 1 - alpha (timescale <= 0: the reference's 86400 s; calc_pflx.opt has
+ * it as a compile-time constant, here it is a run-time argument) and
+ * allocates, zeroed, the three filter states u_slow, v_slow, p_slow (N levels),
+ * up, vp and an N-level work array for p_fast; on = 0 disarms and frees; a
+ * refused call (-1 with N < 2, -2 without memory) leaves an earlier arming as
+ * it was.  Arming again starts from zero states.
+ * While armed, every corrector prsgrd -- roms_gpu_prsgrd with t->nrhs == 3 and
+ * the one inside roms_gpu_step; never the predictor's -- is followed by two
+ * launches (whole steps are then enqueued rather than replayed; the model
+ * fields are bitwise those of the default):
+ *  P over 0..Lm x 0..Mm by prsgrd's expressions (SPLIT_EOS or not, pot_tides),
+ *    p_slow = beta*p_slow + alpha*P, p_fast = P - p_slow;
+ *  Uflx = FlxU(.,.,1) + .. + FlxU(.,.,N) in that order, then Uflx*(pn(i,j)+
+ *    pn(i-1,j))/(z_w(i,j,N)-z_w(i,j,0)+z_w(i-1,j,N)-z_w(i-1,j,0)); Vflx alike
+ *    with pm and j-1; for k = 1..N  u_slow = beta*u_slow + alpha*(u(nrhs)-Uflx),
+ *    u_fast = u(nrhs)-Uflx-u_slow, up = up + u_fast*0.25*(p_fast(i-1,j)+
+ *    p_fast(i,j))*(Hz(i-1,j,k)+Hz(i,j,k)); v_slow, vp alike in j.
+ * Ranges (this rank's indices): p_slow 0..Lm x 0..Mm, u_slow 1..Lm+1 x 1..Mm,
+ * v_slow 1..Lm x 1..Mm+1, up, vp 1..Lm x 1..Mm; nothing is masked; dzt, which
+ * the reference forms and nothing reads, is not formed.  One deviation: at a
+ * physical western edge the reference's prsgrd leaves P(0,j,:) unwritten and
+ * calc_pressure_flux reads it into p_slow(0,j,:) and up(1,j); here P(0,j,:) is
+ * formed like every other column (all its inputs exist).
+ * roms_gpu_pflx_state: a query (any pointer may be NULL); nsamples counts the
+ * correctors filtered since arming.
+ * roms_gpu_pflx_path: launches of the P walk since arming that formed z_r,
+ * z_w(N) from the kept free surface, and that streamed them (same bits;
+ * roms_gpu_time_pflx's launches count too).
+ * roms_gpu_pflx_copy_out(which, dst, count): ROMS_PFLX_UP, VP as (Mm+4, Lm+4),
+ * U_SLOW, V_SLOW, P_SLOW as (N, Mm+4, Lm+4) in the host layout of
+ * roms_gpu_copy_out, zero outside the ranges above: the up(pos,:) lines a
+ * host-side adjust_orlanski (sponge_tune.F:178-198) needs; adjust_orlanski
+ * itself and ub_* stay with the host.  roms_gpu_pflx_copy_in: the three filter
+ * states only (-1 for up, vp), whole arrays in the same layout.  Both -4 when
+ * not armed.
+ * Restart: while armed roms_gpu_wrt_rst also writes u_slow (time, s_rho,
+ * eta_rho, xi_u), v_slow (.., eta_v, xi_rho), p_slow (.., eta_rho, xi_rho),
+ * double, over the write ranges of u, v and a rho field (basic_output.F:977-
+ * 990, wrt_rst_diag_slow); not armed the file is byte for byte what it was.
+ * roms_gpu_get_init while armed follows get_init_slow per variable: read if
+ * present, then 0 where umask / vmask / rmask < 1 (p_slow: its halo exchanged
+ * first); if absent u_slow = u(tindx), v_slow = v(tindx) over their write
+ * ranges, p_slow = 0, and roms_gpu_last_error holds a WARNING line naming each
+ * fallback while the call returns 0.  Arm before roms_gpu_get_init.
+ * roms_gpu_time_pflx: n launches of each kernel between two events, total
+ * milliseconds: ms[0] the P and p_slow walk, ms[1] the u, v walk (the filters
+ * go on from their state: re-arm before they are used).                     */
+#define ROMS_PFLX_UP 1
+#define ROMS_PFLX_VP 2
+#define ROMS_PFLX_U_SLOW 3
+#define ROMS_PFLX_V_SLOW 4
+#define ROMS_PFLX_P_SLOW 5
+int roms_gpu_pflx_begin(double timescale, int on);
+int roms_gpu_pflx_state(int *armed, double *alpha, long *nsamples);
+int roms_gpu_pflx_path(long *formed, long *streamed);
+int roms_gpu_pflx_copy_out(int which, double *dst, long count);
+int roms_gpu_pflx_copy_in(int which, const double *src, long count);
+int roms_gpu_time_pflx(int n, double ms[2]);
 /* ---- z-level slices on the device (ABI 26): calc_zslice / sigma_to_z /
  * calc_average / wrt_zslice of zslice_output.F.  u, v and chosen tracers, slot
  * t->nnew (the slot roms_gpu_wrt_his samples), interpolated from the model
@@ -905,10 +968,17 @@ int roms_gpu_time_calc_zslice(int n, const roms_tlev *t, double *ms);
  * 'grid1', '_west'); a variable is called set_var+bnd.  output_vars is
  * searched for substrings as findstr does: 'zeta', 'temp', 'salt', 'ubar',
  * 'vbar', 'u' (also found in 'ubar' and 'up'), 'v', 'w', 'up', 'vp', 'bgc'.
- * ROMS_EXT_UP/VP/W/BGC are not produced (no calc_pflx or BGC here; w: see ABI 29 above):
- * they are reported in the object's `unsupported` mask and named in
+ * ROMS_EXT_UP/VP are produced for an object added while the pressure fluxes
+ * are armed (roms_gpu_pflx_begin, ABI 34): up = cosa*ui - sina*vi, vp =
+ * sina*ui + cosa*vi with ui, vi the device's up, vp (zero outside 1..Lm x
+ * 1..Mm, halos exchanged) interpolated with the u and the v coefficients; 2-D
+ * variables <set>_up<bnd>, <set>_vp<bnd> on (time, np), 'pressure flux',
+ * 'W/m^2', never remapped; roms_gpu_calc_extract returns -4 if the fluxes were
+ * disarmed since.  Added while not armed they are not produced, like
+ * ROMS_EXT_W/BGC (no BGC here; w: see ABI 29 above): those
+ * are reported in the object's `unsupported` mask and named in
  * roms_gpu_last_error while the call returns 0.  'salt' is ignored without
- * SALINITY.  Refused (-1, nothing armed): a vector variable on a scalar
+ * SALINITY.  Refused (-1, nothing armed): a vector variable (up, vp too) on a scalar
  * object; a 3-D variable with the remap when N < 5.  Coefficients follow
  * compute_coef at rho (+0.5,+0.5), u (+0.5 in i) and v (-0.5 in i, +0.5 in j)
  * positions with rmask/umask/vmask and coef/sum(coef): a point whose four

@@ -45,7 +45,8 @@ namespace {
 
 constexpr int kExtAhead = 4;   // levels whose corner loads one trip of a walk has in flight
 constexpr int kExtSupported = ROMS_EXT_ZETA | ROMS_EXT_UBAR | ROMS_EXT_VBAR | ROMS_EXT_U | ROMS_EXT_V | ROMS_EXT_TEMP | ROMS_EXT_SALT;
-constexpr int kExtVector = ROMS_EXT_UBAR | ROMS_EXT_VBAR | ROMS_EXT_U | ROMS_EXT_V;
+constexpr int kExtPflx = ROMS_EXT_UP | ROMS_EXT_VP;   // produced for objects added while the pressure fluxes are armed (k_pflx.hip)
+constexpr int kExtVector = ROMS_EXT_UBAR | ROMS_EXT_VBAR | ROMS_EXT_U | ROMS_EXT_V | kExtPflx;
 constexpr int kExt3d = ROMS_EXT_U | ROMS_EXT_V | ROMS_EXT_TEMP | ROMS_EXT_SALT;
 // 3-D variable slots: 0 u, 1 v, 2 temp, 3 salt; their grid types 1 u, 2 v, 0 rho
 __host__ __device__ constexpr int ext_bit3(int v) { return v == 0 ? ROMS_EXT_U : v == 1 ? ROMS_EXT_V : v == 2 ? ROMS_EXT_TEMP : ROMS_EXT_SALT; }
@@ -144,6 +145,27 @@ __global__ void __launch_bounds__(64) k_ext_interp(ExtArgs a) {
     if (a.mismatch && (vars & ROMS_EXT_U)) ext_walk(a.Hz_u + o[1], nx2, n2, N, c[1], a.hzp[1] + p, NP);
     if (a.mismatch && (vars & ROMS_EXT_V)) ext_walk(a.Hz_v + o[2], nx2, n2, N, c[2], a.hzp[2] + p, NP);
   }
+}
+
+// up, vp (extract_data.F:764-770, 815-821): upe, vpe interpolated with the u and the v coefficients, rotated.  A
+// launch of its own beside k_ext_interp, taken only while an object asks for them
+struct ExtPfArgs {
+  int NP, nx2;
+  const int *iju, *ijv, *vars;
+  const double *cfu, *cfv, *cosa, *sina;
+  const double *upe, *vpe;   // up, vp inside 1..nx x 1..ny, 0 elsewhere, halos exchanged
+  double *oup, *ovp;         // (NP)
+};
+__global__ void __launch_bounds__(64) k_ext_pflx(ExtPfArgs a) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.NP) return;
+  const int vars = a.vars[p], NP = a.NP;
+  if (!(vars & kExtPflx)) return;
+  const double ui = ext_at(a.upe + a.iju[p], a.nx2, a.cfu[p], a.cfu[(long)NP + p], a.cfu[(long)2 * NP + p], a.cfu[(long)3 * NP + p]);
+  const double vi = ext_at(a.vpe + a.ijv[p], a.nx2, a.cfv[p], a.cfv[(long)NP + p], a.cfv[(long)2 * NP + p], a.cfv[(long)3 * NP + p]);
+  const double cs = a.cosa[p], sn = a.sina[p];
+  if (vars & ROMS_EXT_UP) a.oup[p] = cs * ui - sn * vi;
+  if (vars & ROMS_EXT_VP) a.ovp[p] = sn * ui + cs * vi;
 }
 
 // x**n of the reference, n = 1..4, as products
@@ -336,6 +358,8 @@ struct ExtCtx {
   int NP = 0;
   std::vector<void*> dev;                       // every device allocation
   ExtArgs a{};
+  double *oup = nullptr, *ovp = nullptr;        // up, vp of every point (NP; among dev)
+  double *upe_base = nullptr, *vpe_base = nullptr, *upe = nullptr, *vpe = nullptr;   // extract_data.F's upe, vpe: one plane each
   double* pack = nullptr;
   size_t pack_n = 0;
 };
@@ -349,10 +373,13 @@ void ext_release_device() {
   E.pack = nullptr;
   E.pack_n = 0;
   E.a = ExtArgs{};
+  E.oup = E.ovp = nullptr;
   E.built = E.sampled = false;
 }
 void ext_release() {
   ext_release_device();
+  if (E.upe_base) (void)hipFree(E.upe_base);
+  if (E.vpe_base) (void)hipFree(E.vpe_base);
   E = ExtCtx{};
   shim_extract_huv(false);
 }
@@ -479,6 +506,7 @@ int ext_build(const ShimState& S) {
   up(hvars.data(), (size_t)NP * sizeof(int), dv);
   a.cosa = dcs; a.sina = dsn; a.vars = dv;
   for (int q = 0; q < 3; q++) a.o2[q] = ext_alloc<double>(NP, S.s, oom);
+  if (un & kExtPflx) { E.oup = ext_alloc<double>(NP, S.s, oom); E.ovp = ext_alloc<double>(NP, S.s, oom); }
   for (int v = 0; v < 4; v++) {
     if (!(un & ext_bit3(v))) continue;
     a.prof[v] = ext_alloc<double>((size_t)N * NP, S.s, oom);
@@ -527,6 +555,39 @@ void ext_slots(const ShimState& S, const roms_tlev& t) {
 void ext_launch_interp(const ShimState& S) {
   hipLaunchKernelGGL(k_ext_interp, dim3((E.NP + 63) / 64, 3), dim3(64), 0, S.s, E.a);
 }
+void ext_launch_pflx(const ShimState& S) {
+  const ExtArgs& a = E.a;
+  const ExtPfArgs q{a.NP, a.nx2, a.ij[1], a.ij[2], a.vars, a.cf[1], a.cf[2], a.cosa, a.sina, E.upe, E.vpe, E.oup, E.ovp};
+  hipLaunchKernelGGL(k_ext_pflx, dim3((E.NP + 63) / 64), dim3(64), 0, S.s, q);
+}
+// upe(1:nx,1:ny) = up, vpe alike, and their halos (extract_data.F:598-604): every rank of a decomposed run takes part
+int ext_pflx_planes(const ShimState& S, const char* who) {
+  const PflxView pf = pflx_view();
+  if (!pf.armed) {
+    *S.err = std::string(who) + ": an object asks for up, vp but the pressure fluxes were disarmed since it was added "
+                                "(roms_gpu_pflx_begin)";
+    return -4;
+  }
+  const Bounds& b = S.d->b;
+  const size_t n = (size_t)(b.n2 + kRowAlign) * sizeof(double);
+  const long lead = ((uintptr_t)S.d->f.u / sizeof(double)) % kRowAlign;   // the alignment of the model's fields
+  if (!E.upe_base) {
+    if (hipMalloc(&E.upe_base, n) != hipSuccess || hipMalloc(&E.vpe_base, n) != hipSuccess ||
+        hipMemsetAsync(E.upe_base, 0, n, S.s) != hipSuccess || hipMemsetAsync(E.vpe_base, 0, n, S.s) != hipSuccess) {
+      *S.err = std::string(who) + ": allocation of upe, vpe failed";
+      return -2;
+    }
+    E.upe = E.upe_base + lead;
+    E.vpe = E.vpe_base + lead;
+  }
+  if (hipMemcpyAsync(E.upe, pf.up, (size_t)b.n2 * sizeof(double), hipMemcpyDeviceToDevice, S.s) != hipSuccess ||
+      hipMemcpyAsync(E.vpe, pf.vp, (size_t)b.n2 * sizeof(double), hipMemcpyDeviceToDevice, S.s) != hipSuccess) {
+    *S.err = std::string(who) + ": copy of up, vp failed";
+    return -2;
+  }
+  launch_exchange_list(*S.d, S.s, ExchList{{E.upe, E.vpe}, {1, 1}, 2});
+  return 0;
+}
 void ext_launch_remap(const ShimState& S) {
   hipLaunchKernelGGL(k_ext_remap, dim3((E.NP + 63) / 64), dim3(64, 4), 0, S.s, E.a);
 }
@@ -545,11 +606,13 @@ int ext_prepare(const ShimState& S, const roms_tlev* t, const char* who) {
   if (ext_build(S)) { *S.err = std::string(who) + ": allocation of the extraction buffers failed"; return -2; }
   ext_slots(S, *t);
   if (ext_need_huv()) launch_exchange_list(*S.d, S.s, ExchList{{S.d->f.Hz_u, S.d->f.Hz_v}, {S.d->b.N, S.d->b.N}, 2});
+  if (ext_union() & kExtPflx) return ext_pflx_planes(S, who);
   return 0;
 }
 int ext_sample(const ShimState& S) {
   if (E.NP > 0) {
     ext_launch_interp(S);
+    if (ext_union() & kExtPflx) ext_launch_pflx(S);
     if (E.mismatch && (ext_union() & kExt3d)) ext_launch_remap(S);
   }
   E.sampled = true;
@@ -563,16 +626,20 @@ ExtOut ext_out(const ExtObject& o, int bit) {
   if (bit == ROMS_EXT_ZETA) return {a.o2[0] + o.p0, 1};
   if (bit == ROMS_EXT_UBAR) return {a.o2[1] + o.p0, 1};
   if (bit == ROMS_EXT_VBAR) return {a.o2[2] + o.p0, 1};
+  if (bit == ROMS_EXT_UP) return {E.oup + o.p0, 1};
+  if (bit == ROMS_EXT_VP) return {E.ovp + o.p0, 1};
   const int v = bit == ROMS_EXT_U ? 0 : bit == ROMS_EXT_V ? 1 : bit == ROMS_EXT_TEMP ? 2 : 3;
   if (E.mismatch) return {a.outc[v] + o.p0, E.Nc};
   return {a.prof[v] + o.p0, a.N};
 }
 
-const int kExtOrder[7] = {ROMS_EXT_ZETA, ROMS_EXT_UBAR, ROMS_EXT_VBAR, ROMS_EXT_TEMP, ROMS_EXT_SALT, ROMS_EXT_U, ROMS_EXT_V};   // create_edata_vars
+const int kExtOrder[9] = {ROMS_EXT_ZETA, ROMS_EXT_UBAR, ROMS_EXT_VBAR, ROMS_EXT_TEMP, ROMS_EXT_SALT, ROMS_EXT_U, ROMS_EXT_V,
+                          ROMS_EXT_UP, ROMS_EXT_VP};   // create_edata_vars
 const char* ext_vname(int bit) {
   switch (bit) {
     case ROMS_EXT_ZETA: return "zeta"; case ROMS_EXT_UBAR: return "ubar"; case ROMS_EXT_VBAR: return "vbar";
-    case ROMS_EXT_U: return "u"; case ROMS_EXT_V: return "v"; case ROMS_EXT_TEMP: return "temp"; default: return "salt";
+    case ROMS_EXT_U: return "u"; case ROMS_EXT_V: return "v"; case ROMS_EXT_TEMP: return "temp";
+    case ROMS_EXT_UP: return "up"; case ROMS_EXT_VP: return "vp"; default: return "salt";
   }
 }
 void ext_meta(int bit, std::string& ln, std::string& un) {   // the history table's long_name and units
@@ -583,6 +650,7 @@ void ext_meta(int bit, std::string& ln, std::string& un) {   // the history tabl
     case ROMS_EXT_U: ln = "u-momentum component"; un = "meter second-1"; break;
     case ROMS_EXT_V: ln = "v-momentum component"; un = "meter second-1"; break;
     case ROMS_EXT_TEMP: ln = "potential temperature"; un = "Celsius"; break;
+    case ROMS_EXT_UP: case ROMS_EXT_VP: ln = "pressure flux"; un = "W/m^2"; break;   // create_var without an index (:954-957)
     default: ln = "salinity"; un = "PSU"; break;
   }
 }
@@ -633,10 +701,13 @@ int ext_add(const ShimState& S, const char* name, const char* dname, long npg, c
   if (ext_find(ov, "vp")) f |= ROMS_EXT_VP;
   if (ext_find(ov, "bgc")) f |= ROMS_EXT_BGC;
   if (!S.cfg->salinity || b.NT < 2) f &= ~ROMS_EXT_SALT;   // #ifdef SALINITY
-  o.vars = f & kExtSupported;
-  o.unsupported = f & ~kExtSupported;
+  // up, vp are produced for an object added while the pressure fluxes are armed (roms_gpu_pflx_begin); otherwise
+  // they stay unsupported, as the reference refuses them without calc_pflx
+  const int can = kExtSupported | (pflx_view().armed ? kExtPflx : 0);
+  o.vars = f & can;
+  o.unsupported = f & ~can;
   if (o.scalar && (o.vars & kExtVector)) {
-    *S.err = "roms_gpu_extract_add_object: " + o.name + " asks for a vector variable (ubar, vbar, u, v) but is a scalar "
+    *S.err = "roms_gpu_extract_add_object: " + o.name + " asks for a vector variable (ubar, vbar, u, v, up, vp) but is a scalar "
              "object (no angle column)";
     return -1;
   }
@@ -930,7 +1001,7 @@ int roms_gpu_extract_copy_out(int iobj, int var_bit, double* dst, long count) {
   if (r) return r;
   const ExtObject* o = ext_obj(iobj);
   if (!o) { *S.err = "roms_gpu_extract_copy_out: no such object"; return -1; }
-  if (!(var_bit & kExtSupported) || (var_bit & (var_bit - 1))) { *S.err = "roms_gpu_extract_copy_out: var_bit must be one ROMS_EXT_* bit"; return -1; }
+  if (!(var_bit & (kExtSupported | kExtPflx)) || (var_bit & (var_bit - 1))) { *S.err = "roms_gpu_extract_copy_out: var_bit must be one ROMS_EXT_* bit"; return -1; }
   if (!(o->vars & var_bit) || !dst) { *S.err = "roms_gpu_extract_copy_out: that variable is not extracted for this object"; return -4; }
   if (!E.sampled || !E.built) { *S.err = "roms_gpu_extract_copy_out: no sample yet (roms_gpu_calc_extract)"; return -4; }
   const int rows = (var_bit & kExt3d) ? (E.mismatch ? E.Nc : S.d->b.N) : 1;

@@ -576,6 +576,11 @@ void uvdiag_uv1_begin(const Dev& d, hipStream_t s, const Tlev& t);
 void uvdiag_uv1_end(const Dev& d, hipStream_t s, const Tlev& t);
 void uvdiag_visc3d(const Dev& d, hipStream_t s, const Tlev& t);
 void uvdiag_uv2(const Dev& d, hipStream_t s, const Tlev& t);
+// Baroclinic pressure fluxes (k_pflx.hip; calc_pflx): while armed (pflx_armed, a host flag of the calling thread) every
+// corrector prsgrd is followed by pflx_corrector -- in whole steps and in the roms_gpu_prsgrd entry with nrhs == 3 --
+// which filters P, u, v(nrhs) and forms up, vp: two launches on s
+bool pflx_armed();
+void pflx_corrector(const Dev& d, hipStream_t s, const Tlev& t);
 void launch_u3dbc(const Dev& d, hipStream_t s, const Tlev& t);
 // river_frc.F hooks (k_river.hip): ubar/vbar(knew) and DU/DV_avg1 at river
 // faces after each fast step; u,v(nnew) at river faces (pred: predictor ranges)

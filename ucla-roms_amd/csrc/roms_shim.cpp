@@ -430,6 +430,7 @@ void free_all() {
   wvl_free();
   tdiag_free();
   uvdiag_free();
+  pflx_free();
   zslice_free();
   extract_free();
   part_free();
@@ -631,6 +632,9 @@ void enqueue_step(roms_tlev* t, bool rho_current, bool store_huv) {
   if (g.cfg.lmd_mixing) { TIMED(ROMS_R_LMD_VMIX, DEFER(launch_lmd_vmix(d, s, T, T.nrhs, lean_akt))); akt_lmd_done(); }   // Akv, Akt, hbls, hbbl
   frc_step_phase(d, s, 3, pot);     // set_bry_all 'forward' + set_tides (main.F:438-441)
   TIMED(ROMS_R_PRSGRD, launch_prsgrd(d, s, T, fuse_corr ? 1 : -1, p_ready));
+  // calc_pressure_flux at the end of the corrector's prsgrd (prsgrd.F:466-468; k_pflx.hip): it reads what prsgrd
+  // read (rho1, qp1, the grid) and u, v(nrhs), FlxU, FlxV, whose exchanges are joined above, and writes its own arrays
+  if (pflx_armed()) pflx_corrector(d, s, T);
   XJOIN_T(16, xt);   // step3d_uv1 reads We and Akv across the halo
   TIMED(ROMS_R_STEP3D_UV1, launch_step3d_uv1(d, s, T, fuse_corr, lean_uv));
   if (g.cfg.uv_vis2) TIMED(ROMS_R_VISC3D, launch_visc3d(d, s, T));
@@ -1255,7 +1259,7 @@ int roms_gpu_sync(void) {
   }
 ROUTINE(roms_gpu_set_huv, (launch_set_huv(g.d, g.s, T), g.hzuv_valid = true))
 ROUTINE(roms_gpu_omega, launch_omega(g.d, g.s, T))
-ROUTINE(roms_gpu_prsgrd, launch_prsgrd(g.d, g.s, T))
+ROUTINE(roms_gpu_prsgrd, (launch_prsgrd(g.d, g.s, T), T.nrhs == 3 && pflx_armed() ? pflx_corrector(g.d, g.s, T) : (void)0))
 ROUTINE(roms_gpu_pre_step3d, ((void)akt_sync(), launch_pre_step3d(g.d, g.s, T)))
 ROUTINE(roms_gpu_set_huv1, launch_set_huv1(g.d, g.s, T))
 ROUTINE(roms_gpu_step3d_uv1, launch_step3d_uv1(g.d, g.s, T))
@@ -1573,8 +1577,9 @@ int roms_gpu_step(roms_tlev* t) {
   const bool first = (t->iic == t->forw_start);
   const bool store_huv = g.hzuv_env || g.hzuv_ext || g.f[ROMS_Hz_u].host != nullptr || g.f[ROMS_Hz_v].host != nullptr;
   g.hzuv_valid = store_huv;
-  // while the tracer budget terms are sampled the corrector's extra launches carry the step's own 1/navg: no replay
-  if (!g.use_graphs || first || tdiag_sampling() || uvdiag_sampling()) {
+  // while the tracer budget terms are sampled the corrector's extra launches carry the step's own 1/navg: no replay;
+  // nor while the pressure fluxes are armed (their launches and sample count belong to no captured graph)
+  if (!g.use_graphs || first || tdiag_sampling() || uvdiag_sampling() || pflx_armed()) {
     enqueue_step(t, rho_current, store_huv);
     return post_launch();
   }

@@ -222,6 +222,13 @@ std::vector<OutVar> record_vars(const ShimState& S, const roms_tlev& t, bool rst
   const bool kpp = S.cfg->lmd_mixing != 0;
   if (kpp && (rst || (mask & ROMS_WRT_HBLS))) add("hbls", "Thickness of KPP surface boundary layer", "meter", 'r', 0, av ? av->hbls : F.hbls, 0);
   if (kpp && (rst || (mask & ROMS_WRT_HBBL))) add("hbbl", "Thickness of KPP bottom boundary layer", "meter", 'r', 0, av ? av->hbbl : F.hbbl, 0);
+  // calc_pflx: the filter states while armed (wrt_rst_diag_slow, calc_pflx_mod.F:261-275; defined basic_output.F:977-990)
+  const PflxView pf = pflx_view();
+  if (rst && pf.armed) {
+    add("u_slow", "time filtered u", "m/s", 'u', N, pf.u_slow, n2);
+    add("v_slow", "time filtered v", "m/s", 'v', N, pf.v_slow, n2);
+    add("p_slow", "time filtered pressure", "Pa??", 'r', N, pf.p_slow, n2);
+  }
   if (rst) {
     add("riv_umask", "river mask at u points", "nondim", 'u', 0, F.riv_uflx, 0);
     v.back().slab.as_mask = 1;
@@ -719,6 +726,59 @@ int roms_gpu_get_init(const char* path, int req_rec, int tindx, roms_tlev* t, do
           upload(buf, hd[q], 'r', 1, 0);
           exch(hd[q], 1);
         }
+    }
+    // get_init_slow (calc_pflx_mod.F:173-259) while the pressure fluxes are armed: each filter state over its
+    // write range if the file has it, then 0 where its mask is < 1; else u_slow = u(tindx), v_slow = v(tindx),
+    // p_slow = 0, named in roms_gpu_last_error while the call succeeds
+    const PflxView pf = pflx_view();
+    if (pf.armed) {
+      // 0 where m < 1 on every level of a packed slab
+      auto zero_land = [&](std::vector<double>& q, char g, const std::vector<double>& m) {
+        const Slab s = slab_of(b, p, nullptr, g, N, 0);
+        const int i0 = g == 'u' ? 1 : p.i0, j0 = g == 'v' ? 1 : p.j0;
+        for (int k = 0; k < s.nk; k++)
+          for (int j = 0; j < s.nj; j++)
+            for (int i = 0; i < s.ni; i++)
+              if (m[IJ(b, i0 + i, j0 + j)] < 1.0) q[i + (long)s.ni * (j + (long)s.nj * k)] = 0.0;
+      };
+      // the write range of slot tindx of a model field, packed
+      auto from_field = [&](const double* dev, char g, std::vector<double>& q) {
+        std::vector<double> h((size_t)b.n3);
+        if (copy_on(h.data(), dev + (long)(tindx - 1) * b.n3, (size_t)b.n3 * 8, hipMemcpyDeviceToHost, S.s) != hipSuccess)
+          throw std::runtime_error("download failed");
+        const Slab s = slab_of(b, p, nullptr, g, N, 0);
+        const int i0 = g == 'u' ? 1 : p.i0, j0 = g == 'v' ? 1 : p.j0;
+        q.resize((size_t)s.ni * s.nj * s.nk);
+        for (int k = 0; k < s.nk; k++)
+          for (int j = 0; j < s.nj; j++)
+            for (int i = 0; i < s.ni; i++)
+              q[i + (long)s.ni * (j + (long)s.nj * k)] = h[IJ(b, i0 + i, j0 + j) + (long)k * n2];
+      };
+      std::string missing;
+      if (read_slab("u_slow", 'u', N, buf)) zero_land(buf, 'u', umask);
+      else { from_field(F.u, 'u', buf); missing += " u_slow (initialised to u)"; }
+      upload(buf, pf.u_slow, 'u', N, sk);
+      if (read_slab("v_slow", 'v', N, buf)) zero_land(buf, 'v', vmask);
+      else { from_field(F.v, 'v', buf); missing += " v_slow (initialised to v)"; }
+      upload(buf, pf.v_slow, 'v', N, sk);
+      if (read_slab("p_slow", 'r', N, buf)) {
+        upload(buf, pf.p_slow, 'r', N, sk);
+        exch(pf.p_slow, N);   // up, vp read p_slow across the rank edge
+        // the mask goes over 0..nx x 0..ny after the exchange: the whole array again, masked on the host
+        const long rows = (long)N * (b.Mm + 4);
+        std::vector<double> h((size_t)rows * (b.Lm + 4));
+        if (shim_rows_d2h(h.data(), pf.p_slow, rows) != hipSuccess) throw std::runtime_error("download failed");
+        for (int k = 0; k < N; k++)
+          for (int j = 0; j <= b.Mm; j++)
+            for (int i = 0; i <= b.Lm; i++)
+              if (rmask[IJ(b, i, j)] < 1.0) h[(i + 1) + (long)(b.Lm + 4) * ((j + 1) + (long)(b.Mm + 4) * k)] = 0.0;
+        if (shim_rows_h2d(pf.p_slow, h.data(), rows) != hipSuccess) throw std::runtime_error("upload failed");
+      } else {
+        if (hipMemsetAsync(pf.p_slow, 0, (size_t)b.n3 * 8, S.s) != hipSuccess || hipStreamSynchronize(S.s) != hipSuccess)
+          throw std::runtime_error("zero fill failed");
+        missing += " p_slow (initialised to 0.0)";
+      }
+      if (!missing.empty()) *S.err = std::string("roms_gpu_get_init: ") + path + ": WARNING: not in the initial file:" + missing;
     }
   } catch (const std::exception& e) {
     *S.err = std::string("roms_gpu_get_init: ") + path + ": " + e.what();

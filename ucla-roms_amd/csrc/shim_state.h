@@ -1,5 +1,5 @@
 // shim_state.h -- what the C-ABI modules outside roms_shim.cpp (rst_io.hip and
-// the output producers k_avg, k_zslice, k_extract, k_wvlcty, k_tdiag, k_uvdiag, k_particles)
+// the output producers k_avg, k_zslice, k_extract, k_wvlcty, k_tdiag, k_uvdiag, k_particles, k_pflx)
 // share: the calling thread's library state, the record description a producer
 // hands the writer, the event timer of the roms_gpu_time_* entries, and the
 // few calls the producers make into one another.
@@ -154,6 +154,14 @@ bool tdiag_record(const ShimState& S, std::vector<OutVar>& vars, bool* do_avg, b
 void tdiag_window_written();   // a record took the window
 void tdiag_free();             // roms_gpu_finalize
 void uvdiag_free();            // roms_gpu_finalize
+// Baroclinic pressure fluxes (k_pflx.hip): the filter states of the restart file and up, vp of the extraction, each in
+// the device layout of one slot of u (up, vp: one plane); nullptr while not armed
+struct PflxView {
+  bool armed = false;
+  double *u_slow = nullptr, *v_slow = nullptr, *p_slow = nullptr, *up = nullptr, *vp = nullptr;
+};
+PflxView pflx_view();
+void pflx_free();              // roms_gpu_finalize
 void zslice_free();            // roms_gpu_finalize
 // Akt(isalt) made current on the library stream before a kernel or copy reads it (whole steps may leave it
 // unformed while it is Akt(itemp) bit for bit: roms_shim.cpp akt_stale)

@@ -174,6 +174,12 @@ def load_library(path=LIB_PATH):
     L.roms_gpu_wrt_diag.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                     P(Tlev)]
     L.roms_gpu_time_uvdiag.argtypes = [ctypes.c_int, P(Tlev), P(ctypes.c_double)]
+    L.roms_gpu_pflx_begin.argtypes = [ctypes.c_double, ctypes.c_int]
+    L.roms_gpu_pflx_state.argtypes = [P(ctypes.c_int), P(ctypes.c_double), P(ctypes.c_long)]
+    L.roms_gpu_pflx_path.argtypes = [P(ctypes.c_long), P(ctypes.c_long)]
+    L.roms_gpu_pflx_copy_out.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_pflx_copy_in.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_long]
+    L.roms_gpu_time_pflx.argtypes = [ctypes.c_int, P(ctypes.c_double)]
     L.roms_gpu_zslice_begin.argtypes = [ctypes.c_int, ctypes.c_int, P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int),
                                         ctypes.c_int]
     L.roms_gpu_calc_zslice.argtypes = [P(Tlev)]
@@ -277,7 +283,9 @@ TDIA = dict(advx=1, advy=2, advz=3, mixx=4, mixy=5, mixz=6, snap=7)
 # ROMS_UVD_* of include/roms_gpu.h (diagnostics.F:56-63; prev: u, v(nnew) as step3d_uv1 got them, for budget closure)
 UVD = dict(pgr=1, cor=2, adv=3, dis=4, hmx=5, vmx=6, cpl=7, prev=8)
 UVD_COMP = dict(u=0, v=1)
-# ROMS_EXT_* of include/roms_gpu.h (the output_vars of an extraction object); up, vp, w, bgc are reported, not produced
+PFLX = dict(up=1, vp=2, u_slow=3, v_slow=4, p_slow=5)   # ROMS_PFLX_*
+# ROMS_EXT_* of include/roms_gpu.h (the output_vars of an extraction object); w, bgc are reported, not produced, and so
+# are up, vp of an object added while the pressure fluxes are not armed (pflx_begin)
 EXT = dict(zeta=1, ubar=2, vbar=4, u=8, v=16, temp=32, salt=64, up=128, vp=256, w=512, bgc=1024)
 EXT_3D = ("u", "v", "temp", "salt")
 
@@ -959,6 +967,48 @@ class Model:
         """(ms of n launches of the snapshots, of k_uvdiag_rhs, of k_uvdiag_hmx, of k_uvdiag_cpl)."""
         ms = (ctypes.c_double * 4)()
         self._chk(self.L.roms_gpu_time_uvdiag(n, ctypes.byref(self.t), ms), "time_uvdiag")
+        return tuple(ms)
+
+    # ---- baroclinic pressure fluxes (calc_pflx_mod.F) ----
+    def pflx_begin(self, timescale=0.0, on=True):
+        """Arm calc_pressure_flux after every corrector prsgrd with alpha = dt/timescale (timescale <= 0: the
+        reference's 86400 s), the filter states zero; on=False: disarm and free."""
+        self._chk(self.L.roms_gpu_pflx_begin(float(timescale), int(on)), "pflx_begin")
+
+    def pflx_state(self):
+        """(armed, alpha, nsamples): nsamples counts the correctors filtered since arming."""
+        a, al, n = ctypes.c_int(), ctypes.c_double(), ctypes.c_long()
+        self._chk(self.L.roms_gpu_pflx_state(ctypes.byref(a), ctypes.byref(al), ctypes.byref(n)), "pflx_state")
+        return bool(a.value), al.value, n.value
+
+    def pflx_path(self):
+        """(formed, streamed): k_pflx_p launches since arming that formed the vertical grid from the free surface, and
+        that streamed z_r, z_w."""
+        a, b = ctypes.c_long(), ctypes.c_long()
+        self._chk(self.L.roms_gpu_pflx_path(ctypes.byref(a), ctypes.byref(b)), "pflx_path")
+        return a.value, b.value
+
+    def pflx(self, name):
+        """PFLX array `name`: "up", "vp" as (Mm+4, Lm+4), "u_slow", "v_slow", "p_slow" as (N, Mm+4, Lm+4), like get();
+        0 outside the array's range."""
+        if name not in PFLX:
+            raise ValueError("pflx: unknown array %s" % name)
+        shape = self.shape2 if name in ("up", "vp") else (self.N,) + self.shape2
+        a = np.empty(int(np.prod(shape)), dtype=np.float64)
+        self._chk(self.L.roms_gpu_pflx_copy_out(PFLX[name], a.ctypes.data, a.size), "pflx_copy_out " + name)
+        return a.reshape(shape)
+
+    def pflx_set(self, name, a):
+        """Set a filter state ("u_slow", "v_slow", "p_slow") from an (N, Mm+4, Lm+4) array."""
+        if name not in PFLX:
+            raise ValueError("pflx_set: unknown array %s" % name)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        self._chk(self.L.roms_gpu_pflx_copy_in(PFLX[name], a.ctypes.data, a.size), "pflx_copy_in " + name)
+
+    def time_pflx(self, n):
+        """(ms of n launches of k_pflx_p, of k_pflx_uv)."""
+        ms = (ctypes.c_double * 2)()
+        self._chk(self.L.roms_gpu_time_pflx(n, ms), "time_pflx")
         return tuple(ms)
 
     # ---- z-level slices (calc_zslice / wrt_zslice, zslice_output.F) ----
